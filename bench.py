@@ -17,11 +17,22 @@ curve); a 512 MiB buffer is rewritten between timed steps so no rank's shard
 sits in the 256 MiB Infinity Cache; each step is bracketed by barriers and
 its time summed.
 
-At N=1 the headline is configs[1] (1 GiB uniform); a side result carries
-configs[2] (1 GiB Zipf(1.2), the general pack/decode kernels) with its own
-kernels, roofline and cpu_baseline (--side none skips it).
+At N=1 the headline is configs[1] (1 GiB uniform). A plain run sets up, warms
+up, times the K steps and prints the headline line (value, ms_per_step, the
+sampled kernel times of those steps). --full adds everything that takes runs
+of its own: encode / decode / index-free decode apart ("e2e"), the measured
+HBM ceilings, cpu_baseline, the other scaling mode, the general kernels on the
+headline workload, the .hff file path, and a side result carrying configs[2]
+(1 GiB Zipf(1.2), the general pack/decode kernels) with its own kernels,
+roofline and cpu_baseline (--side none skips it).
+
+--dump-outputs DIR writes what the last timed step computed (the compressed
+stream, its bit count, the code table and the decoded bytes) as DIR/<name>.npy
+after the timed steps; the inputs are generated from fixed seeds, so two
+builds can be compared output for output.
 
 Run: python bench.py [--gpus N --steps K --warmup W --workload uniform|zipf|text]
+                     [--full] [--dump-outputs DIR]
      N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
 import argparse
@@ -304,9 +315,53 @@ def make_input(s: Setup, kind: str, n: int):
     return x, src
 
 
-def run_workload(s: Setup, kind: str, n: int, with_cpu: bool, strong: bool = False):
+DUMP_SAMPLE = 4 << 20  # bytes sampled from an array too large to dump whole (16 MiB as float32)
+DUMP_BLOCK = 1 << 20  # block size of the byte sums that cover a sampled array completely
+DUMP_SEED = 0x5EED0D
+
+
+def dump_outputs(path: str, s: Setup, tree, bits: int, comp: torch.Tensor, dec: torch.Tensor, n: int):
+    """--dump-outputs: what the last timed step handed its caller, as
+    <path>/<name>.npy (float32, or float64 where float32 is not exact; rank r
+    of several writes <name>_rank<r>.npy): the bit count, the code table, the
+    compressed stream and the decoded bytes. A stream longer than DUMP_SAMPLE
+    bytes is written as the bytes at DUMP_SAMPLE positions drawn once from
+    DUMP_SEED (ascending; the same positions for the same length) and, so that
+    every byte counts, the byte sums of its DUMP_BLOCK-sized blocks: 40 MB in
+    all at most."""
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{s.rank}" if s.world > 1 else ""
+
+    def save(name, a):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+
+    def stream(name, t, length):
+        if length <= DUMP_SAMPLE:
+            save(name, t[:length].cpu().numpy().astype(np.float32))
+            return
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, length, DUMP_SAMPLE))
+        save(name + "_sample", t[torch.from_numpy(pos).to(t.device)].cpu().numpy().astype(np.float32))
+        full = length // DUMP_BLOCK
+        sums = t[:full * DUMP_BLOCK].view(full, DUMP_BLOCK).sum(dim=1, dtype=torch.int64)
+        if length % DUMP_BLOCK:
+            sums = torch.cat([sums, t[full * DUMP_BLOCK:length].sum(dtype=torch.int64).reshape(1)])
+        save(name + "_block_sums", sums.cpu().numpy().astype(np.float64))  # < 2^28 each: exact
+
+    torch.cuda.synchronize()
+    code, ln = tree.code_table()
+    save("compressed_bits", np.array([bits], np.float64))
+    save("code_lengths", np.asarray(ln).astype(np.float32))
+    save("codes", np.asarray(code).astype(np.float64))  # exact below 2^53 (codes of <= 53 bits)
+    stream("compressed", comp, (bits + 7) // 8)
+    stream("decoded", dec, n)
+
+
+def run_workload(s: Setup, kind: str, n: int, with_cpu: bool, strong: bool = False, full: bool = True,
+                 dump_dir=None):
     """one bench record: `strong` times each step alone after an Infinity
-    Cache flush (SURVEY §8d's strong-scaling curve), else back to back"""
+    Cache flush (SURVEY §8d's strong-scaling curve), else back to back.
+    `full` adds what takes runs of its own (e2e, the measured ceilings);
+    `dump_dir` gets the last timed step's outputs (dump_outputs)"""
     args, world, rank = s.args, s.world, s.rank
     flush = s.flush_buffer() if strong else None
     ctx = s.ctx
@@ -363,7 +418,7 @@ def run_workload(s: Setup, kind: str, n: int, with_cpu: bool, strong: bool = Fal
     for i in range(args.warmup):
         step(i + 1 < args.warmup)
     torch.cuda.synchronize()
-    if not args.no_verify:
+    if args.warmup and not args.no_verify:
         assert torch.equal(dec[:n], x[:n]), "decode(encode(x)) != x"
 
     # timed region: K steps (weak: back to back; strong: each step alone,
@@ -398,35 +453,40 @@ def run_workload(s: Setup, kind: str, n: int, with_cpu: bool, strong: bool = Fal
     elapsed = s.max_over_ranks(elapsed)
     kstats = {k: ctx.kernel_time(k) for k in ("hist", "chunk_bits", "scan", "pack", "decode")}
     ctx.set_timing(False)
-
-    # end-to-end encode and decode apart (same K, same buffers)
-    s.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        tree, bits = encode_grow()
-    torch.cuda.synchronize()
-    t_enc = s.max_over_ranks(time.perf_counter() - t0)
-    s.barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        job.decode(tree, state["out"].data_ptr(), dec.data_ptr())
-    torch.cuda.synchronize()
-    t_dec = s.max_over_ranks(time.perf_counter() - t0)
-
-    # index-free decode (huff_dev_decompress, comp.rs:487-519): the same
-    # stream as the reference holds it, without the restart index
+    if not args.warmup and not args.no_verify:  # no warm-up step to check: the last timed step's output
+        assert torch.equal(dec[:n], x[:n]), "decode(encode(x)) != x"
+    if dump_dir:
+        dump_outputs(dump_dir, s, tree, bits, state["out"], dec, n)
     comp_bytes = (bits + 7) // 8
-    pad = (8 - bits % 8) % 8
-    got = D.decompress_dev(ctx, tree, state["out"].data_ptr(), comp_bytes, pad, dec.data_ptr(), n + 64)
-    torch.cuda.synchronize()
-    assert got == n and (args.no_verify or torch.equal(dec[:n], x[:n])), "index-free decode != x"
-    s.barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        D.decompress_dev(ctx, tree, state["out"].data_ptr(), comp_bytes, pad, dec.data_ptr(), n + 64)
-    torch.cuda.synchronize()
-    t_idx = s.max_over_ranks(time.perf_counter() - t0)
+
+    if full:
+        # end-to-end encode and decode apart (same K, same buffers)
+        s.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            tree, bits = encode_grow()
+        torch.cuda.synchronize()
+        t_enc = s.max_over_ranks(time.perf_counter() - t0)
+        s.barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            job.decode(tree, state["out"].data_ptr(), dec.data_ptr())
+        torch.cuda.synchronize()
+        t_dec = s.max_over_ranks(time.perf_counter() - t0)
+
+        # index-free decode (huff_dev_decompress, comp.rs:487-519): the same
+        # stream as the reference holds it, without the restart index
+        pad = (8 - bits % 8) % 8
+        got = D.decompress_dev(ctx, tree, state["out"].data_ptr(), comp_bytes, pad, dec.data_ptr(), n + 64)
+        torch.cuda.synchronize()
+        assert got == n and (args.no_verify or torch.equal(dec[:n], x[:n])), "index-free decode != x"
+        s.barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            D.decompress_dev(ctx, tree, state["out"].data_ptr(), comp_bytes, pad, dec.data_ptr(), n + 64)
+        torch.cuda.synchronize()
+        t_idx = s.max_over_ranks(time.perf_counter() - t0)
 
     _, ln = tree.code_table()  # letters present in the input are exactly those with a code
     present = np.asarray(ln) > 0
@@ -455,18 +515,6 @@ def run_workload(s: Setup, kind: str, n: int, with_cpu: bool, strong: bool = Fal
     # the committed PMC summaries are per launch of a 1 GiB job: other sizes get none
     traffic, traffic_src = (dominant_traffic(kind, dom, fixed8, dec_kernel) if n == 1 << 30 else (None, None))
     enc_ms = sum(kernels[k]["avg_ms"] for k in ("hist", "chunk_bits", "scan", "pack") if k in kernels)
-    if s.ceil is None:  # measured HBM ceilings of this GPU, same run (huff_dev_calibrate)
-        s.ceil = D.calibrate(ctx, x.data_ptr(), dec.data_ptr(), n & ~15, 5)
-    read_ceil, copy_ceil = s.ceil
-    # the index-free decode against the roofline: C + N algorithmic bytes over
-    # its wall time per call (the host read of the letter count included), and
-    # the pipeline's PMC bytes when a summary exists for this workload at 1 GiB
-    idx_ach = (comp_bytes + n) / (t_idx / args.steps) / 1e9
-    idx_traffic, idx_src = indexfree_traffic(kind, fixed8) if n == 1 << 30 else (None, None)
-    indexfree_roofline = {"algo_bytes": comp_bytes + n, "achieved": round(idx_ach, 1), "unit": "GB/s",
-                          "frac": round(idx_ach / HBM_PEAK_GBPS, 4), "traffic": idx_traffic,
-                          "traffic_x_algo": round(idx_traffic / (comp_bytes + n), 3) if idx_traffic else None,
-                          "traffic_source": idx_src}
     collective = None
     if world > 1:
         how = ("huff_mgpu_compress (library RCCL communicator)" if s.comm is not None
@@ -494,26 +542,39 @@ def run_workload(s: Setup, kind: str, n: int, with_cpu: bool, strong: bool = Fal
                    "parallelism": f"shard{world}", "collective": collective,
                    "rccl_world": s.rccl_world},
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                     "ceilings_measured": {"read_GBps": round(read_ceil, 1), "copy_GBps": round(copy_ceil, 1),
-                                           "how": "huff_dev_calibrate: 16-B nontemporal stream, best of 5"},
-                     "frac_of_copy_ceiling": round(ach / copy_ceil, 4)},
+                     "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src},
         "kernels": kernels,
         "kernel_timing_every": every,  # kernels[*].launches: the sampled steps
         "pipelined": pipe,
-        "e2e": {"encode_GBps": round(world * n / (t_enc / args.steps) / 1e9, 1),
-                "decode_GBps": round(world * n / (t_dec / args.steps) / 1e9, 1),
-                "encode_ms": round(t_enc * 1e3 / args.steps, 4), "decode_ms": round(t_dec * 1e3 / args.steps, 4),
-                "indexfree_decode_GBps": round(world * n / (t_idx / args.steps) / 1e9, 1),
-                "indexfree_decode_ms": round(t_idx * 1e3 / args.steps, 4),
-                "indexfree_roofline": indexfree_roofline,
-                "note": "encode = pass 1 + host tree + pass 2 (+ the collective at N>1); decode = restart-index "
-                        "decode; indexfree = huff_dev_decompress of the bare stream (spec/fix/scan/mark/decode, "
-                        "one host read of the symbol count)"},
         "kernel_enc_GBps": round(n / (enc_ms * 1e-3) / 1e9, 1),
         "host_gap_ms": round(ms_per_step - sum(k["avg_ms"] for k in kernels.values()), 4),
         "kernel_dec_GBps": kernels.get("decode", {}).get("GBps"),
     }
+    if full:
+        if s.ceil is None:  # measured HBM ceilings of this GPU, same run (huff_dev_calibrate)
+            s.ceil = D.calibrate(ctx, x.data_ptr(), dec.data_ptr(), n & ~15, 5)
+        read_ceil, copy_ceil = s.ceil
+        r["roofline"]["ceilings_measured"] = {"read_GBps": round(read_ceil, 1), "copy_GBps": round(copy_ceil, 1),
+                                              "how": "huff_dev_calibrate: 16-B nontemporal stream, best of 5"}
+        r["roofline"]["frac_of_copy_ceiling"] = round(ach / copy_ceil, 4)
+        # the index-free decode against the roofline: C + N algorithmic bytes over
+        # its wall time per call (the host read of the letter count included), and
+        # the pipeline's PMC bytes when a summary exists for this workload at 1 GiB
+        idx_ach = (comp_bytes + n) / (t_idx / args.steps) / 1e9
+        idx_traffic, idx_src = indexfree_traffic(kind, fixed8) if n == 1 << 30 else (None, None)
+        indexfree_roofline = {"algo_bytes": comp_bytes + n, "achieved": round(idx_ach, 1), "unit": "GB/s",
+                              "frac": round(idx_ach / HBM_PEAK_GBPS, 4), "traffic": idx_traffic,
+                              "traffic_x_algo": round(idx_traffic / (comp_bytes + n), 3) if idx_traffic else None,
+                              "traffic_source": idx_src}
+        r["e2e"] = {"encode_GBps": round(world * n / (t_enc / args.steps) / 1e9, 1),
+                    "decode_GBps": round(world * n / (t_dec / args.steps) / 1e9, 1),
+                    "encode_ms": round(t_enc * 1e3 / args.steps, 4), "decode_ms": round(t_dec * 1e3 / args.steps, 4),
+                    "indexfree_decode_GBps": round(world * n / (t_idx / args.steps) / 1e9, 1),
+                    "indexfree_decode_ms": round(t_idx * 1e3 / args.steps, 4),
+                    "indexfree_roofline": indexfree_roofline,
+                    "note": "encode = pass 1 + host tree + pass 2 (+ the collective at N>1); decode = restart-index "
+                            "decode; indexfree = huff_dev_decompress of the bare stream (spec/fix/scan/mark/decode, "
+                            "one host read of the symbol count)"}
     if s.comm_note:
         r["config"]["collective_note"] = s.comm_note
     if with_cpu:
@@ -648,7 +709,19 @@ def main():
                     help="kernel durations (HIP events) sampled on every Nth timed step")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the N>1 path with several ranks on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: e2e encode / decode / index-free decode, the "
+                         "HBM ceilings, cpu_baseline, 'scaling_other', 'general', 'side' and 'file_path' (each "
+                         "still switched off by its own option); without it only the headline's steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (compressed stream, bit count, code table, decoded "
+                         "bytes) as DIR/<name>.npy; streams over 4 MiB as a seeded sample plus block sums")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the headline
+        args.no_other_scaling = args.no_general = args.no_cpu_baseline = True
+        args.side = args.file_path = "none"
     rc = rank_guard(args)
     if rc is not None:
         sys.exit(rc)
@@ -671,7 +744,8 @@ def main():
     n_strong = (args.total_bytes // world) & ~0xFFFF
     strong = args.scaling == "strong"
     with_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
-    result = run_workload(s, args.workload, n_strong if strong else n_weak, with_cpu, strong)
+    result = run_workload(s, args.workload, n_strong if strong else n_weak, with_cpu, strong, args.full,
+                          args.dump_outputs)
     if not args.no_other_scaling:
         # the 1/2/4/8 curve of the metric is strong scaling of 1 GiB
         # (1 GiB / N per rank, caches flushed); the weak line (1 GiB per rank)

@@ -13,6 +13,6 @@ for w in uniform zipf text; do
   done
 done
 for w in uniform zipf text; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --workload $w > "$out/bench_$w.json" 2> "$out/bench_$w.err"
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload $w > "$out/bench_$w.json" 2> "$out/bench_$w.err"
 done
 echo "gpu_ab $tag done"

@@ -12,10 +12,10 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --t
 tail -2 $out/gpu_tests.log
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 || { tail -20 $out/smoke.log; exit 1; }
 tail -1 $out/smoke.log
-timeout -k 10 300 python -u bench.py > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 echo "bench done"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/bench_trace -o run --output-format csv -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --file-path none > $out/bench_trace.log 2>&1 || { tail -20 $out/bench_trace.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/bench_trace -o run --output-format csv -- python3 $root/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --file-path none > $out/bench_trace.log 2>&1 || { tail -20 $out/bench_trace.log; exit 1; }
 echo "bench trace done"
 cd $root
 for wl in uniform zipf text; do

@@ -17,8 +17,8 @@ for f in device none; do
 done
 HUFF_TIME_MARKERS=1 timeout -k 10 200 python -u tools/timing_ab.py --steps 20 --reps 3 > $out/ab_markers_b.txt 2>&1 || { tail -5 $out/ab_markers_b.txt; exit 1; }
 grep -H '{' $out/ab_*.txt
-timeout -k 10 200 python -u bench.py $B > $out/bench_ext.json 2> $out/bench_ext.err || { tail -5 $out/bench_ext.err; exit 1; }
-HUFF_TIME_MARKERS=1 timeout -k 10 200 python -u bench.py $B > $out/bench_markers.json 2> $out/bench_markers.err || { tail -5 $out/bench_markers.err; exit 1; }
+timeout -k 10 200 python -u bench.py --full $B > $out/bench_ext.json 2> $out/bench_ext.err || { tail -5 $out/bench_ext.err; exit 1; }
+HUFF_TIME_MARKERS=1 timeout -k 10 200 python -u bench.py --full $B > $out/bench_markers.json 2> $out/bench_markers.err || { tail -5 $out/bench_markers.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/prof -o run --output-format csv -- python3 $root/bench.py $B > $out/prof.log 2>&1 || { tail -5 $out/prof.log; exit 1; }
+timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/prof -o run --output-format csv -- python3 $root/bench.py --full $B > $out/prof.log 2>&1 || { tail -5 $out/prof.log; exit 1; }
 echo done

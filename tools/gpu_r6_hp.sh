@@ -15,7 +15,7 @@ for r in 1 2; do
     for wl in uniform zipf; do
       env $env timeout -k 10 120 python -u tools/kbench.py --phase hist --workload $wl --iters 20 > $out/hist_${v}_${wl}_$r.json 2> $out/hist_${v}_${wl}_$r.err || { tail -5 $out/hist_${v}_${wl}_$r.err; exit 1; }
     done
-    env $env timeout -k 10 200 python -u bench.py $B > $out/bench_${v}_$r.json 2> $out/bench_${v}_$r.err || { tail -5 $out/bench_${v}_$r.err; exit 1; }
+    env $env timeout -k 10 200 python -u bench.py --full $B > $out/bench_${v}_$r.json 2> $out/bench_${v}_$r.err || { tail -5 $out/bench_${v}_$r.err; exit 1; }
   done
 done
 grep -H hist_ms $out/hist_*.json | sed "s|$out/||"

@@ -11,10 +11,10 @@ B="--side none --no-general --file-path none --no-cpu-baseline --no-other-scalin
 for r in 1 2; do
   for v in default rows0 rp64 rp256; do
     if [ $v = default ]; then env=""; else env="HUFF_LIB_AB=$v"; fi
-    env $env timeout -k 10 200 python -u bench.py $B > $out/${v}_$r.json 2> $out/${v}_$r.err || { tail -5 $out/${v}_$r.err; exit 1; }
+    env $env timeout -k 10 200 python -u bench.py --full $B > $out/${v}_$r.json 2> $out/${v}_$r.err || { tail -5 $out/${v}_$r.err; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).readline()); print(sys.argv[1].split('/')[-1], d['value'], d['ms_per_step'], {k: v['avg_ms'] for k, v in d['kernels'].items()})" $out/${v}_$r.json
   done
 done
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 $root/bench.py $B --time-every 1000 > $out/trace.log 2>&1 || { tail -5 $out/trace.log; exit 1; }
+timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 $root/bench.py --full $B --time-every 1000 > $out/trace.log 2>&1 || { tail -5 $out/trace.log; exit 1; }
 head -12 $out/trace/run_kernel_stats.csv | cut -c1-160

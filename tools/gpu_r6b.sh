@@ -10,7 +10,7 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --t
 tail -2 $out/gpu_tests.log
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 || { tail -20 $out/smoke.log; exit 1; }
 tail -1 $out/smoke.log
-timeout -k 10 400 python -u bench.py > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 echo "bench done"
 [ "${SCALE:-1}" = 0 ] && exit 0
 bash tools/gpu_r6_scale.sh ${tag}_scale
