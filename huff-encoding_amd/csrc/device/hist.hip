@@ -18,7 +18,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kCopies = 32;
-// log2 of the one-shot histogram's LDS copies (k_hist1): 32 copies (32 KiB,
+// log2 of the one-shot histogram's LDS copies (k_hist1x2): 32 copies (32 KiB,
 // conflict-free on any data, 5 workgroups per CU) by default
 #ifndef HUFF_HIST_LOGC
 #define HUFF_HIST_LOGC 5
@@ -112,83 +112,19 @@ __global__ __launch_bounds__(kThreads) void k_hist(const uint8_t* __restrict__ b
     if (total) atomicAdd(&gw[(blockIdx.x % kHistCopies) * 256 + t], static_cast<unsigned long long>(total));
 }
 
-// One chunk per workgroup (one-shot grid: the streaming-read shape that
-// measured fastest on this chip, tools/calib.hip): all 16 loads of a lane are
-// issued before the first count, the chunk's row is written, and the global
-// weights are summed from the rows afterwards (k_rows_sum) instead of with
-// per-workgroup atomics.
-// HUFF_HIST_THREADS: the workgroup's threads (256: 16 loads of 16 B per
-// lane; 512: 8 per lane with twice the waves sharing one LDS histogram)
-#ifndef HUFF_HIST_THREADS
-#define HUFF_HIST_THREADS 256
-#endif
-template <int LOGC, int T = HUFF_HIST_THREADS>
-__global__ __launch_bounds__(T) void k_hist1(const uint8_t* __restrict__ base, uint64_t lo, uint64_t hi,
-                                             uint32_t* __restrict__ chunk_hist,
-                                             unsigned long long* __restrict__ gw) {
-    constexpr uint32_t C = 1u << LOGC;  // LDS copies of the histogram
-    constexpr int NL = kChunk / 16 / T;  // 16-B loads per lane
-    if (blockIdx.x == 0)  // k_rows_sum / k_rows_publish (next on the stream) accumulate into gw
-        for (uint32_t i = threadIdx.x; i < kHistCopies * 256 + 1; i += T) gw[i] = 0;
-    __shared__ __attribute__((aligned(16))) uint32_t h[256 * C];
-    const uint32_t t = threadIdx.x;
-    const uint32_t lane_c = t & (C - 1);
-    const uint32_t c = blockIdx.x;
-    const uint64_t cbeg = static_cast<uint64_t>(c) * kChunk;
-    const bool full = cbeg >= lo && cbeg + kChunk <= hi;
-    uint4 v[NL];
-    if (full) {
-        const uint4* p = reinterpret_cast<const uint4*>(base + cbeg) + t;
-#pragma unroll
-        for (int r = 0; r < NL; ++r) v[r] = ld_nt(p + r * T);
-    }
-    __builtin_amdgcn_sched_barrier(0);  // loads first, no use of v[] hoisted above them
-    uint4* h4 = reinterpret_cast<uint4*>(h);
-#pragma unroll
-    for (uint32_t i = 0; i < 256 * C / 4 / T; ++i) h4[t + i * T] = make_uint4(0, 0, 0, 0);
-    // a bare barrier (no fence): the LDS zeroing is complete, the loads stay in flight
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0), vmcnt/expcnt untouched
-    __builtin_amdgcn_s_barrier();
-    if (full) {
-#pragma unroll
-        for (int r = 0; r < NL; ++r) {
-            count_word<LOGC>(h, v[r].x, lane_c);
-            count_word<LOGC>(h, v[r].y, lane_c);
-            count_word<LOGC>(h, v[r].z, lane_c);
-            count_word<LOGC>(h, v[r].w, lane_c);
-        }
-    } else {
-        for (int r = 0; r < NL; ++r) {
-            const uint64_t off = cbeg + static_cast<uint64_t>(r) * (16 * T) + t * 16;
-            if (off + 16 <= lo || off >= hi) continue;
-            uint4 x;
-            if (off + 16 <= hi) {
-                x = *reinterpret_cast<const uint4*>(base + off);
-            } else {  // never read past hi
-                uint32_t w[4] = {0, 0, 0, 0};
-                for (int k = 0; off + k < hi; ++k) w[k >> 2] |= static_cast<uint32_t>(base[off + k]) << (8 * (k & 3));
-                x = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            count_masked<LOGC>(h, x, off, lo, hi, lane_c);
-        }
-    }
-    __syncthreads();
-    if (t < 256) {
-        uint32_t s = 0;
-#pragma unroll 8
-        for (uint32_t j = 0; j < C; ++j) s += h[(t << LOGC) | ((j + t) & (C - 1))];
-        chunk_hist[static_cast<uint64_t>(c) * 256 + t] = s;
-    }
-}
-
-// Two chunks per 512-thread workgroup sharing ONE 32-copy LDS image: the
+// One-shot grid (the streaming-read shape that measured fastest on this chip,
+// tools/calib.hip): all 16 loads of a lane are issued before the first count,
+// the chunks' rows are written, and the global weights are summed from the
+// rows afterwards (k_rows_sum / k_rows_publish) instead of with per-workgroup
+// atomics.
+// Two chunks per 512-thread workgroup share ONE 32-copy LDS image: the
 // first chunk's threads add 1, the second's 1 << 16 (a copy counts at most
 // 8 threads x 256 bytes = 2,048 of a chunk, so neither half overflows), the
 // halves are split when the copies are summed. Twice the input in flight
-// per byte of LDS (the one-shot grid was LDS-bound at 5 workgroups per CU,
-// 320 KiB in flight against ~450 KiB for the calibration read): same-box
-// pass 1 uniform 0.215 -> 0.210 ms, Zipf 0.198 -> 0.193 (profiles/r05/hist_x2/).
-// The default; k_hist1 stays for HUFF_HIST_X2=0.
+// per byte of LDS (a chunk per 256-thread workgroup was LDS-bound at 5
+// workgroups per CU, 320 KiB in flight against ~450 KiB for the calibration
+// read): same-box pass 1 uniform 0.215 -> 0.210 ms, Zipf 0.198 -> 0.193
+// (profiles/r05/hist_x2/).
 template <int LOGC>
 __global__ __launch_bounds__(512) void k_hist1x2(const uint8_t* __restrict__ base, uint64_t lo, uint64_t hi,
                                                  uint32_t nchunks, uint32_t* __restrict__ chunk_hist,
@@ -279,17 +215,18 @@ __global__ __launch_bounds__(256) void k_rows_sum(const uint32_t* __restrict__ c
     if (s) atomicAdd(&gw[(blockIdx.x % kHistCopies) * 256 + t], static_cast<unsigned long long>(s));
 }
 
-// k_rows_sum and k_hist_publish in one launch (pass 1 with a host reader):
+// k_rows_sum and the publication of the totals in one launch (pass 1 with a
+// host reader):
 // 16 waves per workgroup, a wave per chunk row at a time (16 B per lane,
 // bins 4l..4l+3) with four rows in flight, the waves summed in LDS and added
 // into gw's XCD copy, then the last workgroup to take a ticket
 // (gw[kHistCopies * 256], zeroed by pass 1's first workgroup) publishes the
-// totals as k_hist_publish does. Few workgroups (<= 128): each pays one
-// agent-scope release (an L2 write-back) before its ticket, and a 1,024-group
-// version spent 26 us there (profiles/r06/pipeline).
-#ifndef HUFF_ROWS_PUBLISH
-#define HUFF_ROWS_PUBLISH 1
-#endif
+// totals straight to pinned host memory: word b = total of bin b with the
+// launch's 16-bit sequence tag in bits 48..63 (totals < 2^48). Each word is
+// one 8-byte store, so the host, polling until all 256 tags match, needs no
+// fence, no flag and no device-to-host copy. Few workgroups (<= 128): each
+// pays one agent-scope release (an L2 write-back) before its ticket, and a
+// 1,024-group version spent 26 us there (profiles/r06/pipeline).
 #ifndef HUFF_RP_GROUPS
 #define HUFF_RP_GROUPS 128
 #endif
@@ -349,19 +286,6 @@ __global__ __launch_bounds__(kRpWaves * 64) void k_rows_publish(const uint32_t* 
 #pragma unroll
     for (uint32_t k = 0; k < kHistCopies; ++k)
         tot += __hip_atomic_load(&gw[k * 256 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&host[t], (tag << 48) | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// Pass 1's result straight to pinned host memory: word b = total of bin b
-// with the launch's 16-bit sequence tag in bits 48..63 (totals < 2^48). Each
-// word is one 8-byte store, so the host, polling until all 256 tags match,
-// needs no fence, no flag and no device-to-host copy.
-__global__ __launch_bounds__(256) void k_hist_publish(const unsigned long long* __restrict__ gw,
-                                                      unsigned long long* host, uint64_t tag) {
-    const uint32_t t = threadIdx.x;
-    uint64_t tot = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kHistCopies; ++k) tot += gw[k * 256 + t];
     __hip_atomic_store(&host[t], (tag << 48) | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -531,17 +455,9 @@ hipError_t launch_hist(const uint8_t* base, uint64_t lo, uint64_t hi, uint32_t n
     if (chunk_hist) {  // per-chunk rows wanted: one-shot grid, then the row sum
         // 32 copies: 16 measured equal on uniform bytes and 20 % slower on
         // Zipf (same-address conflicts between lanes l and l + 16)
-// HUFF_HIST_X2=0: k_hist1, one chunk per workgroup (A/B builds)
-#ifndef HUFF_HIST_X2
-#define HUFF_HIST_X2 1
-#endif
-        if (HUFF_HIST_X2)
-            launch_k(k_hist1x2<HUFF_HIST_LOGC>, dim3((nchunks + 1) / 2), dim3(512), 0, s, base, lo, hi, nchunks,
-                               chunk_hist, gw);
-        else
-            launch_k(k_hist1<HUFF_HIST_LOGC>, dim3(nchunks), dim3(HUFF_HIST_THREADS), 0, s, base, lo, hi,
-                               chunk_hist, gw);
-        if (done.host && HUFF_ROWS_PUBLISH) {
+        launch_k(k_hist1x2<HUFF_HIST_LOGC>, dim3((nchunks + 1) / 2), dim3(512), 0, s, base, lo, hi, nchunks,
+                           chunk_hist, gw);
+        if (done.host) {
             // >= 4 rows per wave where the job has them, 128 workgroups at most
             const uint32_t want = (nchunks + 4 * kRpWaves - 1) / (4 * kRpWaves);
             const uint32_t g = want < HUFF_RP_GROUPS ? want : HUFF_RP_GROUPS;
@@ -551,7 +467,6 @@ hipError_t launch_hist(const uint8_t* base, uint64_t lo, uint64_t hi, uint32_t n
         }
         const uint32_t g = nchunks < 512 ? nchunks : 512;
         launch_k(k_rows_sum, dim3(g), dim3(256), 0, s, chunk_hist, nchunks, gw);
-        if (done.host) launch_k(k_hist_publish, dim3(1), dim3(256), 0, s, gw, done.host, done.tag);
         return hipGetLastError();
     }
     uint32_t grid = nchunks < 1024 ? nchunks : 1024;

@@ -518,10 +518,6 @@ __global__ __launch_bounds__(kThreads) void k_spec_lds(IndexlessArgs a) {
     if (a.lead_bits && start) {  // the entry: the lead-in walk's first boundary >= start
         uint64_t p = start > a.lead_bits ? start - a.lead_bits : 0;
         c.init(st, p);
-#ifndef HUFF_LEAD_MULTI
-#define HUFF_LEAD_MULTI 1
-#endif
-#if HUFF_LEAD_MULTI
         // multi-code chunks up to the last window end below start (window ends
         // are boundaries), single codes from there: lead-in 4.0 K -> 2.3 K
         // cycles per wave, Zipf 1.114 -> 1.092 ms (same box)
@@ -544,7 +540,6 @@ __global__ __launch_bounds__(kThreads) void k_spec_lds(IndexlessArgs a) {
                 break;
             }
         }
-#endif
         for (;;) {
             uint32_t L[kChunkSteps];
             c.chunk<SLOW>(L, stab, K, a.lut, Kg);

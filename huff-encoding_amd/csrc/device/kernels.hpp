@@ -133,9 +133,9 @@ struct DecodeArgs {
     // k_decode_fixed: the 3 KiB per-wave stage (8 workgroups per CU instead of
     // 6) for streams of at most kSmallStageBits bits per symbol (fixed_decode_small)
     uint32_t small_stage;
-    // k_decode_fixed: 1 = the persistent LDS-DMA build (decode_wave.hip
-    // k_decode_dma: the next task's input in flight while a task decodes)
-    uint32_t dma_stage;
+    // k_decode_fixed: cap on the lookups per refill (2-4; shallow trees take
+    // 3 or 4 under a cap of 4, the production value; 0 is treated as 2)
+    uint32_t refill_cap;
     // k_decode_fixed self-check build (0: production kernel; 1: checked).
     // err: u32[8] mismatch count + first (task, lane, want, got)
     uint32_t check_mode;
@@ -419,10 +419,6 @@ size_t decode_lds_bytes(uint32_t lut_bits);
 constexpr uint32_t kDecodeFixed = 10;
 constexpr uint32_t kDecodeFixedCheck = 11;
 
-// Pass 1's totals straight to pinned host memory (device-visible pointer):
-// host[b] = (tag << 48) | total_b. host == nullptr: the totals stay in gw.
-// a result published straight to pinned host memory: (tag << 48) | value
-// in one 8-byte store (pass 1's weights, a scan's grand total)
 // Index-free decode in one pass (syncdec.hip): tiles of 256 segments, a lane
 // per segment decoding its letters into registers, an in-tile fix-up, a
 // decoupled look-back over the tiles for the output offsets, letters out
@@ -457,6 +453,10 @@ struct SyncDecArgs {
 size_t sync_decode_lds_bytes(const SyncDecArgs& a);
 hipError_t launch_sync_decode(const SyncDecArgs& a, hipStream_t s);
 
+// Pass 1's totals straight to pinned host memory (device-visible pointer):
+// host[b] = (tag << 48) | total_b. host == nullptr: the totals stay in gw.
+// a result published straight to pinned host memory: (tag << 48) | value
+// in one 8-byte store (pass 1's weights, a scan's grand total)
 struct HistDone {
     unsigned long long* host = nullptr;
     uint64_t tag = 0;  // 16 bits

@@ -79,12 +79,6 @@ __device__ __forceinline__ Staged stage_block(const A& a, uint32_t* w, uint32_t 
 // path per lookup) cost ~40 VALU and ~40 SALU per step in the multi-symbol
 // form this replaces (PMC: 344 K VALU per SIMD per GiB).
 constexpr int kChunkSteps = 8;
-// refills every 3rd / 4th step for tables of <= 10 / <= 8 bits
-// (HUFF_WALK_R=0: every 2nd, for the A/B build)
-#ifndef HUFF_WALK_R
-#define HUFF_WALK_R 1
-#endif
-constexpr bool kWalkR = HUFF_WALK_R != 0;
 
 // lane cursor over the staged range: 64-bit window, valid bits in the low 6
 // bits of X (X -= entry borrows only above them), refilled unconditionally
@@ -192,7 +186,7 @@ struct Cursor {
     // K-bit table (K = min(depth, 12)), so every 4th step for K <= 8, every
     // 3rd for K <= 10, else every 2nd (K is wave-uniform: a scalar branch)
     __device__ __forceinline__ static uint32_t refill_steps(uint32_t K) {
-        return !kWalkR || K > 10 ? 0x55u : K > 8 ? 0x49u : 0x11u;
+        return K > 10 ? 0x55u : K > 8 ? 0x49u : 0x11u;
     }
     template <bool SLOW>
     __device__ __forceinline__ void chunk(uint32_t (&L)[kChunkSteps], const uint16_t* stab, uint32_t K,

@@ -594,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void k_sync_decode(SyncDecArgs a) {
 // The letters k_sync_decode left (lanes re-counted from a new entry, letters
 // past kCap): one job per lane, decoded serially from global memory with the
 // single-symbol table; then the letter count to the host (tagged, as
-// k_hist_publish) once every earlier kernel of the decode is done.
+// k_rows_publish) once every earlier kernel of the decode is done.
 __global__ __launch_bounds__(256) void k_sync_tail(SyncDecArgs a) {
     const uint32_t nj = __hip_atomic_load(a.ctrl + kSyncJobs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint64_t njobs = nj < a.job_cap ? nj : a.job_cap;

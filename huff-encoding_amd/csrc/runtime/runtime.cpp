@@ -58,31 +58,65 @@ huff_compress_data::~huff_compress_data() { delete tree; }
 
 namespace huff {
 
+// The run-time test knobs of the encode and decode paths: environment
+// variables that switch a default path off so that the tests (and bench.py's
+// `general` record) reach the kernels behind it. All of them are read at the
+// time of the call, never cached: tests and the benchmark flip them inside
+// one process. Nothing under csrc/device/ reads the environment.
+//
+//   HUFF_DISABLE_FIXED8=1   the general pack/decode kernels even when every
+//                           code has 8 bits (else the byte map). bench.py
+//                           (`general`); test_gpu_parity, test_gpu_decode_check
+//   HUFF_SMALL_STAGE=0      k_decode_fixed keeps its 4.5 KiB stage for every
+//                           stream (else 3 KiB for <= 5.6 bits per symbol).
+//                           test_gpu_parity
+//   HUFF_DEC_VARIANT=11     k_decode_fixed's self-checking build (any other
+//                           value: the production decoder). test_gpu_decode_check,
+//                           test_gpu_parity, test_gpu_indexfree
+//   HUFF_DEC_REFILL=2|3|4   cap on k_decode_fixed's lookups per refill (default
+//                           4: shallow trees take 3 or 4). test_gpu_parity
+//   HUFF_NO_L2 (set)        the index-free walks read the global multi-level
+//                           table, not the level-2 length table in LDS.
+//                           test_gpu_parity, test_gpu_indexfree
+//   HUFF_L2_SPARSE (set)    the level-2 table's branching walk even where slow
+//                           windows are common (read when a tree's decode
+//                           tables are built). test_gpu_wide
+//   HUFF_WIDE_MARK_WALK (set)  index-free wide-letter decode from exact walked
+//                           marks, not k_mark_lite's skip marks. test_gpu_wide
+//
+// The opt-in one-pass decoder's switch, HUFF_SYNC_DECODE, and its lead-ins
+// stay with decode_sync (below), to leave with it. Diagnostics stay beside
+// the code they report on: HUFF_FIX_STATS (below),
+// HUFF_TIME_FENCE / HUFF_TIME_MARKERS (huff_ctx::timed), HUFF_HOST_TRACE
+// (capi.cpp), HUFF_FILE_* (filepath.cpp).
 bool fixed8_disabled() {
-    const char* e = std::getenv("HUFF_DISABLE_FIXED8");  // read per call: tests flip it
+    const char* e = std::getenv("HUFF_DISABLE_FIXED8");
     return e && *e && *e != '0';
 }
 
-// HUFF_SMALL_STAGE=0: the decoders keep the 4.5 KiB stage for every stream (A/B)
 bool small_stage_enabled() {
-    const char* e = std::getenv("HUFF_SMALL_STAGE");  // read per call: tests flip it
+    const char* e = std::getenv("HUFF_SMALL_STAGE");
     return !(e && *e == '0');
 }
 
-// HUFF_DMA_DECODE=1: the persistent LDS-DMA decoder (k_decode_dma; measured
-// 8-15 % slower than the one-shot register-staged one, profiles/r06/decode_bound/)
-uint32_t dma_decode_enabled() {
-    const char* e = std::getenv("HUFF_DMA_DECODE");  // read per call: tests flip it
-    return (e && *e == '1') ? 1u : 0u;
-}
-
 uint32_t decode_check_mode() {
-    const char* e = std::getenv("HUFF_DEC_VARIANT");  // read per call: tests flip it
+    const char* e = std::getenv("HUFF_DEC_VARIANT");
     if (!e) return 0;
     // 11: k_decode_fixed's self-checking build; every other value is the
     // production decoder (the round-2 diagnostics 12-14 are not in the library)
     return std::atoi(e) == static_cast<int>(dev::kDecodeFixedCheck) ? 1u : 0u;
 }
+
+uint32_t decode_refill_cap() {
+    const char* e = std::getenv("HUFF_DEC_REFILL");
+    return e && e[0] >= '2' && e[0] <= '4' ? static_cast<uint32_t>(e[0] - '0') : 4u;
+}
+
+bool l2_table_disabled() { return std::getenv("HUFF_NO_L2") != nullptr; }
+
+bool l2_sparse_forced() { return std::getenv("HUFF_L2_SPARSE") != nullptr; }
+
+bool wide_mark_walk() { return std::getenv("HUFF_WIDE_MARK_WALK") != nullptr; }
 
 #ifdef HUFF_STAMPS
 // Timing builds only (tools/build_variant.sh -DHUFF_STAMPS): per-wave phase
@@ -264,7 +298,7 @@ static void build_len_l2(const HuffTree& t, const std::vector<std::pair<uint32_t
     std::vector<uint8_t> b;
     if (uniform) {
         out.l2E = Emax;
-        out.l2dense = slow.size() * 64 > (size_t(1) << K) && !std::getenv("HUFF_L2_SPARSE");  // (A/B: =1 branches)
+        out.l2dense = slow.size() * 64 > (size_t(1) << K) && !l2_sparse_forced();
         b.resize(slow.size() << Emax);
         for (size_t s = 0; s < slow.size(); ++s)
             for (uint32_t j = 0; j < (1u << Emax); ++j) b[(s << Emax) + j] = len_below(slow[s].node, Emax, j);
@@ -518,7 +552,7 @@ huff::Status huff_ctx::upload_dec_tables(const huff_tree* t, const huff::DecTabl
 huff::Status huff_enc::init(huff_ctx* c, const uint8_t* d, uint64_t nbytes) {
     if (reinterpret_cast<uintptr_t>(d) & 15)
         return huff::Status::err(HUFF_E_INVALID_ARG, "device input must be 16-byte aligned");
-    if (nbytes >= (1ull << 48))  // pass 1 publishes 48-bit totals (hist.hip, k_hist_publish)
+    if (nbytes >= (1ull << 48))  // pass 1 publishes 48-bit totals (hist.hip, k_rows_publish)
         return huff::Status::err(HUFF_E_INVALID_ARG, "one job holds fewer than 2^48 bytes");
     ctx = c;
     d_in = d;
@@ -580,7 +614,7 @@ huff::Status huff_enc::launch_publish(uint64_t* tag) {
 }
 
 huff::Status huff_enc::wait_weights(uint64_t tag) {
-    // every word carries the launch's tag once written (k_hist_publish)
+    // every word carries the launch's tag once written (k_rows_publish)
     const uint64_t* hw = static_cast<const uint64_t*>(ctx->pin_w.p);
     hipStream_t s = ctx->stream;
     int b = 0;
@@ -959,7 +993,7 @@ huff::Status huff_enc::decode(const huff_tree* t, const uint8_t* d_comp, uint64_
     a.cu_count = static_cast<uint32_t>(ctx->cu_count);
     a.pad_stage = huff::dev::fixed_decode_pad(total_bits, n);
     a.small_stage = huff::small_stage_enabled() && huff::dev::fixed_decode_small(total_bits, n);
-    a.dma_stage = huff::dma_decode_enabled();
+    a.refill_cap = huff::decode_refill_cap();
     a.stab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->soff);
     a.stab_bits = dt->sbits;
     a.n = n;
@@ -1250,7 +1284,7 @@ Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes,
     a.stab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->soff);
     a.stab_bits = dt->sbits;
     a.wtab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->woff);
-    if (dt->l2words && !std::getenv("HUFF_NO_L2")) {  // HUFF_NO_L2=1: the global secondary tables (A/B)
+    if (dt->l2words && !l2_table_disabled()) {  // else the global secondary tables
         a.l2 = static_cast<const uint32_t*>(ctx->d_lut.p) + dt->l2off;
         a.l2_words = dt->l2words;
         a.l2_e = dt->l2E;
@@ -1619,7 +1653,7 @@ Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_
         d.cu_count = static_cast<uint32_t>(ctx->cu_count);
         d.pad_stage = dev::fixed_decode_pad(valid_bits, total);
         d.small_stage = small_stage_enabled() && dev::fixed_decode_small(valid_bits, total);
-        d.dma_stage = dma_decode_enabled();
+        d.refill_cap = decode_refill_cap();
         d.n = total;
         d.out = bounce ? static_cast<uint8_t*>(ctx->d_align.p) : out_at();
         d.check_mode = check;

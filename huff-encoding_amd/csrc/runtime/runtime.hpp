@@ -72,19 +72,29 @@ struct DecTables {
 };
 
 
+// The run-time test knobs (listed with their values and users at their
+// definitions in runtime.cpp; each reads the environment per call).
 // HUFF_DISABLE_FIXED8=1 forces the general kernels even for all-8-bit codes
 bool fixed8_disabled();
+// HUFF_SMALL_STAGE=0 keeps the decoders' 4.5 KiB stage for every stream
+bool small_stage_enabled();
+// HUFF_DEC_VARIANT=11 -> k_decode_fixed's self-checking build (mode 1; else 0)
+uint32_t decode_check_mode();
+// HUFF_DEC_REFILL=2..4 caps k_decode_fixed's lookups per refill (default 4)
+uint32_t decode_refill_cap();
+// HUFF_NO_L2: the index-free walks take the global multi-level table
+bool l2_table_disabled();
+// HUFF_L2_SPARSE: never the dense (branch-free) form of the level-2 table
+bool l2_sparse_forced();
+// HUFF_WIDE_MARK_WALK: index-free wide-letter decode from exact walked marks
+bool wide_mark_walk();
+
 // HUFF_HOST_TRACE: when huff_enc::pack finished its bit count, started and
 // returned from the byte-map launch (this thread's last pack)
 struct PackStamps {
     std::chrono::steady_clock::time_point bits, launch, launched;
 };
 PackStamps& pack_stamps();
-// HUFF_SMALL_STAGE=0 keeps the decoders' 4.5 KiB stage for every stream
-bool small_stage_enabled();
-uint32_t dma_decode_enabled();
-// HUFF_DEC_VARIANT=11 -> k_decode_fixed's self-checking build (mode 1; else 0)
-uint32_t decode_check_mode();
 
 Status build_dec_tables(const HuffTree& t, DecTables& out);
 

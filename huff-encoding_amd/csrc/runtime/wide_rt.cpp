@@ -385,7 +385,7 @@ Status wdecode_indexless_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* 
     st.dt = dt;
     const WideDecTables* wdt = nullptr;
     HUFF_TRY(t->dec_tables(&wdt));
-    const bool skip = !wdt->stab.empty() && !std::getenv("HUFF_WIDE_MARK_WALK");
+    const bool skip = !wdt->stab.empty() && !wide_mark_walk();
     DevBuf& sub_abs = ctx->idx_sub_abs;
     // every kWideRun-th letter: the task decoder (the tree's two-level table)
     // takes k_mark_lite's marks (a boundary and the codes to skip from it, as

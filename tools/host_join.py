@@ -2,7 +2,7 @@
 """Join the host phase stamps of huff_enc_compress (HUFF_HOST_TRACE=1 lines,
 steady_clock ns) with a rocprofv3 kernel trace of the same run (its
 timestamps are on the host's monotonic clock): per step, how long the host
-took to see pass 1's weights after k_hist_publish ended, the tree, the pass-2
+took to see pass 1's weights after k_rows_publish ended, the tree, the pass-2
 launch call, and the launch call to the kernel's start.
 
     python tools/host_join.py host_trace.err trace/run_kernel_trace.csv
@@ -20,7 +20,7 @@ def main():
         if m:
             host.append([int(v) for v in m.groups()])
     rows = sorted(csv.DictReader(open(sys.argv[2])), key=lambda r: int(r["Start_Timestamp"]))
-    pub = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if "k_hist_publish" in r["Kernel_Name"] or "k_rows_publish" in r["Kernel_Name"]]
+    pub = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if "k_rows_publish" in r["Kernel_Name"]]
     h1 = [int(r["Start_Timestamp"]) for r in rows if "k_hist1x2" in r["Kernel_Name"]]
     bm = [int(r["Start_Timestamp"]) for r in rows if "k_bytemap" in r["Kernel_Name"]]
     out = []

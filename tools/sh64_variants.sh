@@ -1,7 +1,8 @@
 #!/usr/bin/env bash
 # Builds the three libraries of the 64-bit-shift bisection (DESIGN.md §3,
 # "The 64-bit shift hazard") from the round-2 wrong-letter reproducer
-# (decode_wave.hip with -DHUFF_DEC_EARLY_LOADS=1), on the CPU:
+# (decode_wave.hip as it stood then: the first task's loads ahead of the table
+# copy, today's only form), on the CPU:
 #   lib/sh64A  the reproducer's assembly, reassembled unchanged
 #   lib/sh64B  the same instructions, k_decode_fixed<PAD>'s allocation raised
 #              from 72 to 80 VGPRs (so v72, the register after the refill
@@ -17,7 +18,7 @@ W=$R/scratch/sh64
 L=/opt/rocm/lib/llvm/bin
 mkdir -p $W
 F=_ZN4huff3dev12_GLOBAL__N_114k_decode_fixedILb1EEEvNS0_10DecodeArgsE
-FL="-std=c++17 -O3 -I$R/include -I$P/csrc --offload-arch=gfx950 -munsafe-fp-atomics -fPIC -DHUFF_DEC_EARLY_LOADS=1"
+FL="-std=c++17 -O3 -I$R/include -I$P/csrc --offload-arch=gfx950 -munsafe-fp-atomics -fPIC"
 /opt/rocm/bin/hipcc $FL --cuda-device-only -S -o $W/repro.s $P/csrc/device/decode_wave.hip 2>/dev/null
 /opt/rocm/bin/hipcc $FL -c -o $W/host.o $P/csrc/device/decode_wave.hip 2>/dev/null
 python3 - "$W" "$F" <<'PY'

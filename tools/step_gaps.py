@@ -12,7 +12,7 @@ import statistics
 
 
 def short(name):
-    for k in ("k_hist1x2", "k_rows_sum", "k_rows_publish", "k_hist_publish", "k_bytemap", "k_pack", "k_decode", "k_chunk_bits",
+    for k in ("k_hist1x2", "k_rows_sum", "k_rows_publish", "k_bytemap", "k_pack", "k_decode", "k_chunk_bits",
               "k_scan"):
         if k in name:
             return k
@@ -35,7 +35,7 @@ def main():
         gap = 0.0 if prev_end is None or not cur else max(0.0, (s - prev_end) / 1e3)
         name = short(r["Kernel_Name"])
         if name == "k_bytemap":  # serial steps: pass 2 follows pass 1, decode follows pass 2
-            name = "k_bytemap(after pass 1)" if last in ("k_hist_publish", "k_rows_sum", "k_rows_publish") else "k_bytemap(after bytemap)"
+            name = "k_bytemap(after pass 1)" if last in ("k_rows_sum", "k_rows_publish") else "k_bytemap(after bytemap)"
         if not name.startswith("__amd"):
             last = name
         cur.append((name, (e - s) / 1e3, gap))
