@@ -1357,8 +1357,12 @@ Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes,
                 unsigned int f[8];
                 HIP_TRY(hipMemcpyAsync(f, st.flag.p, sizeof f, hipMemcpyDeviceToHost, strm));
                 HIP_TRY(hipStreamSynchronize(strm));
-                std::fprintf(stderr, "huff fix-up: segments %llu, listed by the speculative pass %u, chain fixes %u\n",
-                             static_cast<unsigned long long>(nseg), f[dev::kFixRounds], f[dev::kFixRounds + 3]);
+                static_assert(dev::kFixRounds == 4, "the line below prints four round flags");
+                std::fprintf(stderr,
+                             "huff fix-up: segments %llu, listed by the speculative pass %u, chain fixes %u, "
+                             "segment bits %llu, rounds %u %u %u %u\n",
+                             static_cast<unsigned long long>(nseg), f[dev::kFixRounds], f[dev::kFixRounds + 3],
+                             static_cast<unsigned long long>(S), f[0], f[1], f[2], f[3]);
             }
             return Status::ok();
         }
@@ -1606,7 +1610,15 @@ Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_
     if (total == 0) HUFF_TRY(walk_end(nullptr, 0, nullptr, 0));
     HUFF_TRY(out_ptr(total));
     hipStream_t strm = ctx->stream;
-    if (dev::indexless_staged(st.a) && total && !(reinterpret_cast<uintptr_t>(d_comp) & 15)) {
+    if (total == 0) {
+        // no letter to write. (The staged pass leaves st.a.s / c and st.off
+        // unwritten: k_emit below would read what an earlier decode of codes
+        // past 32 bits left there and write that many letters to the output,
+        // which for a count-only query is not even a buffer.)
+        HIP_TRY(hipEventRecord(ctx->lut_free, strm));
+        return Status::ok();
+    }
+    if (dev::indexless_staged(st.a) && !(reinterpret_cast<uintptr_t>(d_comp) & 15)) {
         // a misaligned output: decoded into an aligned buffer, then copied (as huff_enc::decode)
         const bool bounce = reinterpret_cast<uintptr_t>(out_at()) & 15;
         if (bounce) HUFF_TRY(ctx->d_align.ensure(total + 64));

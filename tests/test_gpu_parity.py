@@ -705,9 +705,10 @@ def test_file_path_windows(H, O, ctx, window, piece, monkeypatch):
     HUFF_FILE_WINDOW the decompress windows, so a file crosses many windows,
     each ending inside a code (carried to the next window, realigned when it
     starts inside a byte). Multi-block files (the bug-compatible stitching)
-    and a tree deeper than 57 bits (deep pack, serial deep walk) included;
-    outputs equal the oracle's CLI compress / decompress
-    (huff/src/comp.rs:32-283)"""
+    and 70 letters of equal frequency included (the tree comes from the
+    file's own counts: 6-7-bit codes, not a deep tree; a file whose own tree
+    is 33 bits deep is test_file_path_long_code_tree); outputs equal the
+    oracle's CLI compress / decompress (huff/src/comp.rs:32-283)"""
     monkeypatch.setenv("HUFF_FILE_WINDOW", str(window))
     monkeypatch.setenv("HUFF_FILE_PIECE", str(piece))
     _, _, letters, rng = _fib_tree(H, O, 70, 7)
@@ -724,6 +725,34 @@ def test_file_path_windows(H, O, ctx, window, piece, monkeypatch):
             assert blob == O.cli_compress(src, bs), k
             H.read_decompress_write(p + ".hff", p + ".out", bs, ctx)
             assert open(p + ".out", "rb").read() == O.cli_decompress(blob, bs), (k, window)
+
+
+def test_file_path_long_code_tree(H, O, ctx, monkeypatch):
+    """a file whose own counts give a 33-bit tree: bytes 1 ... 34 with
+    Fibonacci counts 1, 1, 2, ... (14,930,351 bytes; a deeper tree needs a
+    file no test can hold), in 1 MiB pieces and 65,539-byte windows: the
+    long-code packer at piece bit offsets, and the decoder for codes past 32
+    bits (k_spec, k_fix, k_emit) with a window end walked from the last
+    segment's settled start. One block and four stitched blocks; byte-equal
+    to the oracle's CLI compress and decompress"""
+    monkeypatch.setenv("HUFF_FILE_WINDOW", "65539")
+    monkeypatch.setenv("HUFF_FILE_PIECE", "1048576")
+    fib = [1, 1]
+    while len(fib) < 34:
+        fib.append(fib[-1] + fib[-2])
+    src = np.random.default_rng(33).permutation(np.repeat(np.arange(1, 35, dtype=np.uint8), np.array(fib)))
+    assert src.size == 14_930_351
+    assert O.Tree.from_weights(O.weights_from_array(O.fast_hist(src, 8))).code_table()[1].max() >= 33
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "fib34")
+        src.tofile(p)
+        src = src.tobytes()
+        for bs in (2_000_000_000, 4_000_000):
+            H.read_compress_write(p, p + ".hff", bs, ctx)
+            blob = open(p + ".hff", "rb").read()
+            assert blob == O.cli_compress(src, bs), bs
+            H.read_decompress_write(p + ".hff", p + ".out", bs, ctx)
+            assert open(p + ".out", "rb").read() == O.cli_decompress(blob, bs), bs
 
 
 def test_file_path_large(H, O, ctx):
