@@ -51,6 +51,14 @@ const char* huff_last_error(void) { return huff::capi::last_error(); }
 uint8_t huff_last_missing_letter(void) { return huff::capi::last_missing(); }
 const char* huff_version(void) { return "huffgpu 0.1 (gfx950)"; }
 
+// diagnostics: which k_decode_fixed build ran, from which index form
+uint32_t huff_diag_decode_builds(void) { return huff::dev::decode_fixed_builds(); }
+const char* huff_diag_decode_build_name(uint32_t i) { return huff::dev::decode_fixed_build_name(i); }
+uint64_t huff_diag_decode_build_launches(uint32_t i) { return huff::dev::decode_fixed_build_launches(i); }
+uint32_t huff_diag_decode_index_forms(void) { return huff::dev::decode_fixed_index_forms(); }
+const char* huff_diag_decode_index_form_name(uint32_t i) { return huff::dev::decode_fixed_index_form_name(i); }
+uint64_t huff_diag_decode_index_form_launches(uint32_t i) { return huff::dev::decode_fixed_index_form_launches(i); }
+
 // --------------------------------------------------------------------------
 int huff_ctx_create(int device, huff_ctx** out) {
     if (!out) return fail(HUFF_E_INVALID_ARG, "null output");

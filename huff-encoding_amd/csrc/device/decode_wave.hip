@@ -15,6 +15,7 @@
 // Roofline: HBM-bound; algorithmic traffic ceil(bits/8) (read) + n (write)
 // + the restart index (2 B per 64 symbols + 8 B per task in the compact form).
 #include <algorithm>
+#include <atomic>
 
 #include "bitreader.hpp"
 
@@ -614,6 +615,75 @@ static uint32_t lookups_per_refill(uint32_t max_len, uint32_t cap) {
     return r < cap ? r : cap;
 }
 
+// Every compiled build of decode_fixed_body, one row each: the kernel and its
+// name are one token sequence (FX_BUILD), so the name counted is the name of
+// the pointer launched. launch_decode_fixed computes a row number and takes
+// both from the row. (tests/test_decode_builds_host.py holds a case per row.)
+using FixedKernel = void (*)(DecodeArgs);
+struct FixedBuild {
+    FixedKernel kern;
+    const char* name;
+};
+#define FX_BUILD(...) {__VA_ARGS__, #__VA_ARGS__}
+// (The rows' order is the order the kernels are instantiated in, and so their
+// order in the code object: the two-lookup builds first, then the shallow
+// trees', as the code object has had them since the R > 2 builds were added.)
+static const FixedBuild kFixedBuilds[] = {
+    // two lookups per refill. Indexed, every code in the table: [pad]
+    FX_BUILD(k_decode_fixed<false, 2>), FX_BUILD(k_decode_fixed<true, 2>),
+    // indexed, codes past the table: [pad]
+    FX_BUILD(k_decode_fixed_slow<false>), FX_BUILD(k_decode_fixed_slow<true>),
+    // the self-checking build: [slow][pad]
+    FX_BUILD(k_decode_fixed_chk<false, false>), FX_BUILD(k_decode_fixed_chk<false, true>),
+    FX_BUILD(k_decode_fixed_chk<true, false>), FX_BUILD(k_decode_fixed_chk<true, true>),
+    // index-free (skip marks): [slow][pad]
+    FX_BUILD(k_decode_fixed_skip<false, false, false, 2>), FX_BUILD(k_decode_fixed_skip<false, true, false, 2>),
+    FX_BUILD(k_decode_fixed_skip<true, false, false, 2>), FX_BUILD(k_decode_fixed_skip<true, true, false, 2>),
+    // index-free, the small stage, unswizzled (79 VGPRs keep 6 waves per
+    // SIMD; the swizzled body needs 81: 5)
+    FX_BUILD(k_decode_fixed_skip<false, false, true, 2>),
+    // shallow trees, 3 or 4 lookups per refill. Indexed: [R - 3][pad]
+    FX_BUILD(k_decode_fixed<false, 3>), FX_BUILD(k_decode_fixed<true, 3>),
+    FX_BUILD(k_decode_fixed<false, 4>), FX_BUILD(k_decode_fixed<true, 4>),
+    // index-free: [R - 3][pad]
+    FX_BUILD(k_decode_fixed_skip<false, false, false, 3>), FX_BUILD(k_decode_fixed_skip<false, true, false, 3>),
+    FX_BUILD(k_decode_fixed_skip<false, false, false, 4>), FX_BUILD(k_decode_fixed_skip<false, true, false, 4>),
+    // index-free, the small stage: [R - 3]
+    FX_BUILD(k_decode_fixed_skip<false, false, true, 3>), FX_BUILD(k_decode_fixed_skip<false, false, true, 4>),
+};
+#undef FX_BUILD
+constexpr uint32_t kNumFixedBuilds = sizeof(kFixedBuilds) / sizeof(kFixedBuilds[0]);
+enum : uint32_t {
+    kRowFixed = 0, kRowSlow = 2, kRowChk = 4, kRowSkip = 8, kRowSmall = 12,  // R = 2
+    kRowFixedR = 13, kRowSkipR = 17, kRowSmallR = 21,                        // R = 3, 4
+};
+static_assert(kNumFixedBuilds == kRowSmallR + 2, "23 builds");
+static std::atomic<uint64_t> g_build_launches[kNumFixedBuilds];
+
+// The form a launch's tasks read their restart entries in: the fields
+// task_load tests, in its order (its SKIP is the skip builds' = skip_packed)
+static const char* const kIndexForms[] = {"mark32+task_seg", "sub_abs64/skip", "sub_abs64", "sub16+task_base",
+                                          "chunk_start+sub_bit"};
+constexpr uint32_t kNumIndexForms = sizeof(kIndexForms) / sizeof(kIndexForms[0]);
+static std::atomic<uint64_t> g_form_launches[kNumIndexForms];
+static uint32_t index_form(const DecodeArgs& a) {
+    if (a.skip_packed && a.mark32) return 0;
+    if (a.sub_abs64) return a.skip_packed ? 1 : 2;
+    if (a.sub16) return 3;
+    return 4;
+}
+
+uint32_t decode_fixed_builds() { return kNumFixedBuilds; }
+const char* decode_fixed_build_name(uint32_t i) { return i < kNumFixedBuilds ? kFixedBuilds[i].name : nullptr; }
+uint64_t decode_fixed_build_launches(uint32_t i) {
+    return i < kNumFixedBuilds ? g_build_launches[i].load(std::memory_order_relaxed) : 0;
+}
+uint32_t decode_fixed_index_forms() { return kNumIndexForms; }
+const char* decode_fixed_index_form_name(uint32_t i) { return i < kNumIndexForms ? kIndexForms[i] : nullptr; }
+uint64_t decode_fixed_index_form_launches(uint32_t i) {
+    return i < kNumIndexForms ? g_form_launches[i].load(std::memory_order_relaxed) : 0;
+}
+
 hipError_t launch_decode_fixed(const DecodeArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     // the small stage: the skip build with every code in the table (same-box
@@ -625,36 +695,21 @@ hipError_t launch_decode_fixed(const DecodeArgs& a, hipStream_t s) {
     const size_t lds = decode_fixed_lds_bytes(a.stab_bits, small);
     const uint64_t ntasks = (a.n + kTaskSym - 1) / kTaskSym;
     const bool slow = a.max_len > a.stab_bits;
-    const bool pad = a.pad_stage != 0;
-    using K = void (*)(DecodeArgs);
-    // [check mode][slow][pad]
-    static const K table[2][2][2] = {
-        {{k_decode_fixed<false>, k_decode_fixed<true>},
-         {k_decode_fixed_slow<false>, k_decode_fixed_slow<true>}},
-        {{k_decode_fixed_chk<false, false>, k_decode_fixed_chk<false, true>},
-         {k_decode_fixed_chk<true, false>, k_decode_fixed_chk<true, true>}},
-    };
-    static const K skip_table[2][2] = {{k_decode_fixed_skip<false, false, false>, k_decode_fixed_skip<false, true, false>},
-                                       {k_decode_fixed_skip<true, false, false>, k_decode_fixed_skip<true, true, false>}};
-    // the small stage unswizzled: 79 VGPRs keep 6 waves per SIMD (the
-    // swizzled body needs 81: 5)
-    const K small_kern = k_decode_fixed_skip<false, false, true>;
+    const uint32_t pad = a.pad_stage != 0;
     if (a.check_mode > 1 || (a.check_mode && !a.err)) return hipErrorInvalidValue;
     if (a.skip_packed && (a.check_mode || (!a.sub_abs64 && !(a.mark32 && a.task_seg && a.seg_bits))))
         return hipErrorInvalidValue;
-    K kern = small ? small_kern
-                   : (a.skip_packed ? skip_table[slow][pad] : table[a.check_mode][slow][pad]);
     // shallow trees: 3 or 4 lookups per refill (the production builds; a
-    // refill_cap of 2 keeps two, for A/B)
-    const uint32_t r = lookups_per_refill(a.max_len, a.refill_cap);
-    if (!slow && !a.check_mode && r > 2) {
-        static const K fx_r[2][2] = {{k_decode_fixed<false, 3>, k_decode_fixed<true, 3>},
-                                     {k_decode_fixed<false, 4>, k_decode_fixed<true, 4>}};
-        static const K skip_r[2][2] = {{k_decode_fixed_skip<false, false, false, 3>, k_decode_fixed_skip<false, true, false, 3>},
-                                       {k_decode_fixed_skip<false, false, false, 4>, k_decode_fixed_skip<false, true, false, 4>}};
-        static const K small_r[2] = {k_decode_fixed_skip<false, false, true, 3>, k_decode_fixed_skip<false, false, true, 4>};
-        kern = small ? small_r[r - 3] : (a.skip_packed ? skip_r[r - 3][pad] : fx_r[r - 3][pad]);
-    }
+    // refill_cap of 2 keeps two, for A/B); slow codes and the check build: 2
+    const uint32_t cap_r = lookups_per_refill(a.max_len, a.refill_cap);
+    const uint32_t r = !slow && !a.check_mode && cap_r > 2 ? cap_r : 2;
+    const uint32_t row = small            ? (r > 2 ? kRowSmallR + (r - 3) : kRowSmall)
+                         : a.skip_packed ? (r > 2 ? kRowSkipR + 2 * (r - 3) + pad : kRowSkip + 2 * slow + pad)
+                         : a.check_mode  ? kRowChk + 2 * slow + pad
+                         : slow          ? kRowSlow + pad
+                         : r > 2         ? kRowFixedR + 2 * (r - 3) + pad
+                                         : kRowFixed + pad;
+    const FixedKernel kern = kFixedBuilds[row].kern;
     const uint64_t want = (ntasks + kWaves - 1) / kWaves;
     // production: one task per wave (a one-shot grid, as the byte map's): the
     // dispatcher refills the CUs as waves finish — same-box A/B against the
@@ -669,6 +724,8 @@ hipError_t launch_decode_fixed(const DecodeArgs& a, hipStream_t s) {
         cap = uint64_t(a.cu_count ? a.cu_count : 256) * per_cu;
     }
     const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, cap)));
+    g_build_launches[row].fetch_add(1, std::memory_order_relaxed);
+    g_form_launches[index_form(a)].fetch_add(1, std::memory_order_relaxed);
     launch_k(kern, dim3(grid), dim3(kThreads), lds, s, a);
     return hipGetLastError();
 }

@@ -488,6 +488,15 @@ hipError_t launch_scan(const uint64_t* bits, uint32_t nchunks, uint64_t base, ui
 hipError_t launch_pack(bool long_codes, const PackArgs& a, hipStream_t s);
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
 hipError_t launch_decode_fixed(const DecodeArgs& a, hipStream_t s);
+// diagnostics (huffgpu.h huff_diag_decode_*): launch_decode_fixed's table of
+// compiled k_decode_fixed builds and the forms its tasks read their restart
+// entries in, with process-wide launch counts. name: null past the last row.
+uint32_t decode_fixed_builds();
+const char* decode_fixed_build_name(uint32_t i);
+uint64_t decode_fixed_build_launches(uint32_t i);
+uint32_t decode_fixed_index_forms();
+const char* decode_fixed_index_form_name(uint32_t i);
+uint64_t decode_fixed_index_form_launches(uint32_t i);
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

@@ -120,6 +120,12 @@ SIGNATURES = [
     ("huff_file_compress", i, [vp, C.c_char_p, C.c_char_p, sz]),
     ("huff_file_decompress", i, [vp, C.c_char_p, C.c_char_p, sz]),
     ("huff_parse_block_size", i, [C.c_char_p, szp]),
+    ("huff_diag_decode_builds", C.c_uint32, []),
+    ("huff_diag_decode_build_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_decode_build_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_diag_decode_index_forms", C.c_uint32, []),
+    ("huff_diag_decode_index_form_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_decode_index_form_launches", C.c_uint64, [C.c_uint32]),
     # include/huffgpu_wide.h
     ("huff_wtree_from_weights", i, [C.c_uint32, vp, vp, sz, C.POINTER(vp)]),
     ("huff_wtree_clone", i, [vp, C.POINTER(vp)]),
@@ -170,6 +176,21 @@ def load():
             f.argtypes = args
         _lib = L
     return _lib
+
+
+def decode_build_launches() -> dict:
+    """{build name: launches so far} of the fixed-count task decoder's compiled
+    builds (huff_diag_decode_build_*), process-wide, in the launcher's order"""
+    L = load()
+    return {L.huff_diag_decode_build_name(k).decode(): L.huff_diag_decode_build_launches(k)
+            for k in range(L.huff_diag_decode_builds())}
+
+
+def decode_index_form_launches() -> dict:
+    """{index form: launches so far} (huff_diag_decode_index_form_*)"""
+    L = load()
+    return {L.huff_diag_decode_index_form_name(k).decode(): L.huff_diag_decode_index_form_launches(k)
+            for k in range(L.huff_diag_decode_index_forms())}
 
 
 def last_error() -> str:

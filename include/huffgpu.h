@@ -365,6 +365,28 @@ int huff_file_decompress(huff_ctx* ctx, const char* src_path, const char* dst_pa
 /* cli.rs:79-114 parse_block_size ("2G", "64Ki", ...): HUFF_E_INVALID_ARG on error */
 int huff_parse_block_size(const char* s, size_t* out);
 
+/* ------------------------------------------------------------------------ */
+/* diagnostics (not reference functions)                                      */
+/* ------------------------------------------------------------------------ */
+/* Which compiled build of the fixed-count task decoder (k_decode_fixed,
+ * codes <= 32 bits) ran: the launcher takes the kernel from one table of
+ * (kernel, name) rows and counts every launch on the row it launched, process-
+ * wide (all contexts and threads; the counts only grow). builds(): the number
+ * of rows; build_name(i): row i's name, the kernel's own template spelling
+ * (e.g. "k_decode_fixed_skip<false, true, false, 4>"), NULL for i >=
+ * builds(); build_launches(i): launches of row i so far (0 for i >= builds()). */
+uint32_t huff_diag_decode_builds(void);
+const char* huff_diag_decode_build_name(uint32_t i);
+uint64_t huff_diag_decode_build_launches(uint32_t i);
+/* The same for the form in which a launch's tasks read their restart entries:
+ * "sub16+task_base" and "chunk_start+sub_bit" (huff_enc_decode), "sub_abs64"
+ * (exact marks: the self-checking index-free decode), "sub_abs64/skip" (skip
+ * marks as u64: the file path's windows) and "mark32+task_seg" (compact skip
+ * marks: huff_dev_decompress). */
+uint32_t huff_diag_decode_index_forms(void);
+const char* huff_diag_decode_index_form_name(uint32_t i);
+uint64_t huff_diag_decode_index_form_launches(uint32_t i);
+
 #ifdef __cplusplus
 }
 #endif
