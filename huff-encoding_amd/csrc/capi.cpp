@@ -586,6 +586,93 @@ int huff_batch_trees(huff_ctx* ctx, const uint64_t* d_hist, uint32_t nstreams, u
     });
 }
 
+int huff_batch_bits(huff_ctx* ctx, const uint64_t* d_hist, const uint64_t* d_codes, const uint32_t* d_tree_status,
+                    const uint64_t* d_offsets, uint32_t nstreams, uint64_t* d_bits, uint64_t* d_comp_offsets,
+                    uint64_t* d_index_offsets, uint32_t* d_status) {
+    if (!ctx || !d_comp_offsets || !d_index_offsets ||
+        (nstreams && (!d_hist || !d_codes || !d_tree_status || !d_offsets || !d_bits || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    static_assert(static_cast<int>(huff::dev::kBatchInvalid) == static_cast<int>(HUFF_E_INVALID_ARG) &&
+                      static_cast<int>(huff::dev::kBatchMissing) == static_cast<int>(HUFF_E_MISSING_LETTER) &&
+                      static_cast<int>(huff::dev::kBatchCorrupt) == static_cast<int>(HUFF_E_CORRUPT),
+                  "the kernels write the C ABI's status codes");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        huff::dev::BatchBitsArgs a{};
+        a.hist = d_hist;
+        a.codes = d_codes;
+        a.tree_status = d_tree_status;
+        a.off = d_offsets;
+        a.nstreams = nstreams;
+        a.bits = d_bits;
+        a.comp_off = d_comp_offsets;
+        a.idx_off = d_index_offsets;
+        a.status = d_status;
+        HUFF_TRY(ctx->timed("batch_bits", [&] { return huff::dev::launch_batch_bits(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+int huff_batch_pack(huff_ctx* ctx, const uint8_t* d_in, const uint64_t* d_offsets, const uint64_t* d_codes,
+                    const uint64_t* d_bits, const uint64_t* d_comp_offsets, const uint64_t* d_index_offsets,
+                    uint32_t* d_status, uint32_t nstreams, uint8_t* d_out, size_t out_cap, uint32_t* d_sub,
+                    size_t sub_cap) {
+    if (!ctx || !d_comp_offsets || !d_index_offsets ||
+        (nstreams && (!d_offsets || !d_codes || !d_bits || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        // the two totals, before anything is launched
+        uint64_t total[2] = {0, 0};
+        HIP_TRY_RT(hipMemcpyAsync(&total[0], d_comp_offsets + nstreams, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY_RT(hipMemcpyAsync(&total[1], d_index_offsets + nstreams, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HUFF_TRY(ctx->sync());
+        if (total[0] > out_cap || (d_sub && total[1] > sub_cap))
+            return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "batch output or index capacity too small");
+        if ((total[0] && (!d_out || !d_in))) return huff::Status::err(HUFF_E_INVALID_ARG, "null argument");
+        huff::dev::BatchPackArgs a{};
+        a.in = d_in;
+        a.off = d_offsets;
+        a.codes = d_codes;
+        a.bits = d_bits;
+        a.comp_off = d_comp_offsets;
+        a.idx_off = d_index_offsets;
+        a.status = d_status;
+        a.nstreams = nstreams;
+        a.out = d_out;
+        a.sub = d_sub;
+        HUFF_TRY(ctx->timed("batch_pack", [&] { return huff::dev::launch_batch_pack(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+int huff_batch_decode(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                      const uint64_t* d_codes, const uint32_t* d_sub, const uint64_t* d_index_offsets,
+                      const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out,
+                      uint32_t* d_status) {
+    if (!ctx || (nstreams && (!d_comp_offsets || !d_bits || !d_codes || (d_sub && !d_index_offsets) || !d_offsets ||
+                              !d_status_in || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        huff::dev::BatchDecodeArgs a{};
+        a.comp = d_comp;
+        a.comp_off = d_comp_offsets;
+        a.bits = d_bits;
+        a.codes = d_codes;
+        a.sub = d_sub;
+        a.idx_off = d_index_offsets;
+        a.off = d_offsets;
+        a.status_in = d_status_in;
+        a.nstreams = nstreams;
+        a.out = d_out;
+        a.status = d_status;
+        HUFF_TRY(ctx->timed(d_sub ? "batch_decode" : "batch_decode_noindex",
+                            [&] { return huff::dev::launch_batch_decode(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
 int huff_dev_generate(huff_ctx* ctx, int kind, uint64_t seed, uint64_t offset, const uint64_t* cdf, uint8_t* d_out,
                       size_t n) {
     if (!ctx || (!d_out && n) || (kind == 1 && !cdf)) return fail(HUFF_E_INVALID_ARG, "null argument");

@@ -374,6 +374,53 @@ hipError_t launch_hist_batch(const uint8_t* in, const uint64_t* off, uint32_t ns
                              hipStream_t s);
 hipError_t launch_tree_batch(const TreeBatchArgs& a, hipStream_t s);
 
+// compress_with_tree / decompress of every stream of a batch (batch_codec.hip).
+// Stream s = in[off[s], off[s + 1]) (a descending pair: empty); its compressed
+// bytes are out[comp_off[s], comp_off[s + 1]), ceil(bits[s] / 8) of them, and
+// sub[idx_off[s] + j] is the bit offset, from the stream's first bit, of its
+// symbol kIdx * j. Status values are the C ABI's.
+enum : uint32_t { kBatchOk = 0, kBatchInvalid = 1, kBatchMissing = 3, kBatchCorrupt = 19 };
+struct BatchBitsArgs {
+    const uint64_t* hist;         // [nstreams][256]
+    const uint64_t* codes;        // [nstreams][256]: code << 8 | len (TreeBatchArgs::codes)
+    const uint32_t* tree_status;  // [nstreams]: a status other than kBatchOk passes through
+    const uint64_t* off;          // [nstreams + 1]
+    uint32_t nstreams;
+    uint64_t* bits;               // [nstreams]
+    uint64_t* comp_off;           // [nstreams + 1]: exclusive scan of ceil(bits / 8)
+    uint64_t* idx_off;            // [nstreams + 1]: exclusive scan of ceil(n / kIdx)
+    uint32_t* status;             // [nstreams]
+};
+struct BatchPackArgs {
+    const uint8_t* in;
+    const uint64_t* off;
+    const uint64_t* codes;
+    const uint64_t* bits;
+    const uint64_t* comp_off;
+    const uint64_t* idx_off;
+    uint32_t* status;             // streams not kBatchOk write nothing; kBatchInvalid is set where the
+                                  // stream's bytes do not add up to bits[s]
+    uint32_t nstreams;
+    uint8_t* out;
+    uint32_t* sub;                // may be null: no index
+};
+struct BatchDecodeArgs {
+    const uint8_t* comp;
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint64_t* codes;
+    const uint32_t* sub;          // null: one lane walks the whole stream
+    const uint64_t* idx_off;      // unused when sub is null
+    const uint64_t* off;          // the letter counts
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    uint8_t* out;
+    uint32_t* status;             // status_in passed through, kBatchOk or kBatchCorrupt
+};
+hipError_t launch_batch_bits(const BatchBitsArgs& a, hipStream_t s);
+hipError_t launch_batch_pack(const BatchPackArgs& a, hipStream_t s);
+hipError_t launch_batch_decode(const BatchDecodeArgs& a, hipStream_t s);
+
 // codes longer than kLongMaxLen (deep.hip): up to 255 bits, kDeepWords
 // left-aligned words per letter
 constexpr uint32_t kDeepWords = 8;

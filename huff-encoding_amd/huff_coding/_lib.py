@@ -104,6 +104,9 @@ SIGNATURES = [
     ("huff_dev_decompress", i, [vp, vp, vp, sz, C.c_uint8, vp, sz, szp]),
     ("huff_batch_hist", i, [vp, vp, vp, C.c_uint32, vp]),
     ("huff_batch_trees", i, [vp, vp, C.c_uint32, vp, sz, vp, vp, vp, vp]),
+    ("huff_batch_bits", i, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+    ("huff_batch_pack", i, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, sz]),
+    ("huff_batch_decode", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]),
     ("huff_comm_unique_id", i, [vp]),
     ("huff_comm_init", i, [vp, vp, i, i, C.POINTER(vp)]),
     ("huff_comm_free", None, [vp]),

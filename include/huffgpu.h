@@ -333,6 +333,61 @@ int huff_batch_trees(huff_ctx* ctx, const uint64_t* d_hist, uint32_t nstreams, u
                      size_t tree_stride, uint32_t* d_tree_nbits, uint64_t* d_codes, uint32_t* d_max_len,
                      uint32_t* d_status);
 
+/* The batch from code tables to compressed streams and back (device
+ * pointers, synchronous). Stream s is d_in[d_offsets[s],
+ * d_offsets[s + 1]), n_s letters; d_codes[s] is its table as huff_batch_trees
+ * writes it (it need not come from d_hist[s]: one tree's row may be given to
+ * every stream). Each stream is compress_with_tree's stream for it alone
+ * (comp.rs:419-451): d_out[d_comp_offsets[s], d_comp_offsets[s + 1]) holds
+ * ceil(d_bits[s] / 8) bytes, the first code at the first byte's MSB and
+ * (8 - d_bits[s] % 8) % 8 zero pad bits at the end (calc_padding_bits,
+ * utils.rs:37-40); the streams lie tightly one after another. The restart
+ * index: d_sub[d_index_offsets[s] + j] is the bit offset, from the stream's
+ * first bit, of its letter 64 j, for j < ceil(n_s / 64).
+ *  huff_batch_bits:   d_bits[s] = sum over letters of d_hist[s][l] * len of
+ *                     d_codes[s][l] (comp.rs:424-431), d_comp_offsets = the
+ *                     exclusive scan of ceil(d_bits[s] / 8), d_index_offsets =
+ *                     the exclusive scan of ceil(n_s / 64) (both nstreams + 1
+ *                     entries, scanned on the device). d_status[s]: a
+ *                     d_tree_status[s] other than HUFF_OK is kept;
+ *                     HUFF_E_MISSING_LETTER: a letter of d_hist[s] has no code
+ *                     ("letter not found in codes", comp.rs:426);
+ *                     HUFF_E_INVALID_ARG: 2^32 bits or more (the index offsets
+ *                     are 32-bit: such a stream belongs to huff_enc_*). A stream
+ *                     that is not HUFF_OK has 0 bits and 0 bytes.
+ *  huff_batch_pack:   reads the two totals back first and returns
+ *                     HUFF_E_BUFFER_TOO_SMALL, nothing written, if out_cap
+ *                     (bytes) or sub_cap (entries) is short. d_sub NULL: no
+ *                     index. A stream whose d_status is not HUFF_OK writes
+ *                     nothing. Every byte of d_out has one writer; nothing
+ *                     outside a stream's own bytes and entries is written.
+ *                     d_status[s] becomes HUFF_E_INVALID_ARG where the
+ *                     stream's letters do not add up to d_bits[s] (d_hist[s]
+ *                     was not its histogram).
+ *  huff_batch_decode: decompress (comp.rs:487-519) of every stream: n_s
+ *                     letters to d_out + d_offsets[s]. d_sub NULL: index-free
+ *                     (one lane walks each stream; d_index_offsets is not
+ *                     read). d_status[s] = d_status_in[s] if that is not
+ *                     HUFF_OK (nothing written), else HUFF_OK, or
+ *                     HUFF_E_CORRUPT: a window matches no code, or n_s letters
+ *                     do not end exactly at d_bits[s] (with an index: every 64
+ *                     letters at the next entry), or the stream's offsets
+ *                     disagree with d_bits[s] and n_s. A corrupt stream reads
+ *                     only its own compressed bytes, writes only its own n_s
+ *                     output bytes and leaves the other streams alone.
+ *                     d_status may be d_status_in. */
+int huff_batch_bits(huff_ctx* ctx, const uint64_t* d_hist, const uint64_t* d_codes, const uint32_t* d_tree_status,
+                    const uint64_t* d_offsets, uint32_t nstreams, uint64_t* d_bits, uint64_t* d_comp_offsets,
+                    uint64_t* d_index_offsets, uint32_t* d_status);
+int huff_batch_pack(huff_ctx* ctx, const uint8_t* d_in, const uint64_t* d_offsets, const uint64_t* d_codes,
+                    const uint64_t* d_bits, const uint64_t* d_comp_offsets, const uint64_t* d_index_offsets,
+                    uint32_t* d_status, uint32_t nstreams, uint8_t* d_out, size_t out_cap, uint32_t* d_sub,
+                    size_t sub_cap);
+int huff_batch_decode(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                      const uint64_t* d_codes, const uint32_t* d_sub, const uint64_t* d_index_offsets,
+                      const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out,
+                      uint32_t* d_status);
+
 /* synthetic inputs generated on the device (not reference functions):
  * kind 0 = uniform bytes, 1 = Zipf(alpha) with cdf[256] (host), 2 = text.
  * Byte i of the stream depends only on (kind, seed, offset + i). */

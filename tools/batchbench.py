@@ -5,6 +5,14 @@ the library's own host build of the same trees (huff_tree_from_weights +
 as_bin, one thread) beside them.
 
     python tools/batchbench.py --streams 10000 --bytes 16384 --iters 10
+
+--codec adds the batched codec (huff_batch_bits / huff_batch_pack /
+huff_batch_decode) on uniform and Zipf streams of the same shape: kernel
+times and GB/s (of uncompressed bytes) of each call, the wall time of the
+whole batched compress and decompress, and beside them the per-stream route
+(one device job per stream: huff_enc_create + huff_enc_compress, then
+huff_enc_decode) timed over --loop-sample streams and extrapolated to the
+batch.
 """
 import argparse
 import json
@@ -22,12 +30,96 @@ import huff_coding as H  # noqa: E402
 from huff_coding import batch  # noqa: E402
 
 
+def codec(ctx, kind, S, L, iters, loop_sample):
+    """the batched codec on S streams of L bytes of `kind`, and the per-stream
+    device-job loop over loop_sample of them"""
+    from huff_coding import device
+
+    n = S * L
+    data = torch.empty(n, dtype=torch.uint8, device="cuda")
+    device.generate(ctx, kind, 11, data.data_ptr(), n, cdf=device.zipf_cdf(1.2) if kind == "zipf" else None)
+    offs = torch.arange(0, S + 1, device="cuda", dtype=torch.int64) * L
+    c = batch.compress_batch(ctx, data, offs)  # warm-up, and the streams to decode
+    out, st = batch.decompress_batch(ctx, c)
+    torch.cuda.synchronize()
+    assert int((c.status != 0).sum()) == 0 and int((st != 0).sum()) == 0 and torch.equal(out, data)
+    hist = batch.batch_hist(ctx, data, offs)
+    comp = torch.empty_like(c.comp)
+    sub = torch.empty_like(c.sub)
+    ctx.set_timing(True)
+    ctx.reset_timing()
+    for _ in range(iters):
+        bits, coff, ioff, status = batch.batch_bits(ctx, hist, c.trees.codes, c.trees.status, offs)
+        batch.batch_pack(ctx, data, offs, c.trees.codes, bits, coff, ioff, status, comp, sub)
+        batch.batch_decode(ctx, comp, coff, bits, c.trees.codes, sub, ioff, offs, status, out)
+        batch.batch_decode(ctx, comp, coff, bits, c.trees.codes, None, None, offs, status, out)
+    torch.cuda.synchronize()
+    res = {"kind": kind, "comp_ratio": round(c.comp.numel() / n, 4)}
+    for k in ("batch_bits", "batch_pack", "batch_decode", "batch_decode_noindex"):
+        ms, cnt = ctx.kernel_time(k)
+        res[k + "_ms"] = round(ms / cnt, 4)
+        res[k + "_GBps"] = round(n / (ms / cnt * 1e-3) / 1e9, 1)
+    ctx.set_timing(False)
+    # wall time of the whole batched route (hist, trees, bits, pack with their allocations; decode)
+    wc, wd = [], []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        c = batch.compress_batch(ctx, data, offs)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        batch.decompress_batch(ctx, c)
+        torch.cuda.synchronize()
+        wc.append(t1 - t0)
+        wd.append(time.perf_counter() - t1)
+    res["batched_compress_wall_ms"] = round(min(wc) * 1e3, 3)
+    res["batched_decompress_wall_ms"] = round(min(wd) * 1e3, 3)
+    # the per-stream route: one device job per stream
+    m = min(loop_sample, S)
+    if m <= 0:
+        return res
+    cap = L * 2 + 64
+    d_out = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    d_back = torch.empty(L, dtype=torch.uint8, device="cuda")
+
+    def loop(k0, k1):
+        tc = td = 0.0
+        for s in range(k0, k1):
+            t0 = time.perf_counter()
+            job = device.EncodeJob(ctx, data.data_ptr() + s * L, L)
+            tree, _ = job.compress(d_out.data_ptr(), cap)
+            ctx.synchronize()
+            t1 = time.perf_counter()
+            job.decode(tree, d_out.data_ptr(), d_back.data_ptr())
+            ctx.synchronize()
+            t2 = time.perf_counter()
+            job.close()
+            tc += t1 - t0
+            td += t2 - t1
+        return tc, td
+
+    loop(0, min(10, m))  # warm-up
+    tc, td = loop(0, m)
+    torch.cuda.synchronize()
+    assert torch.equal(d_back, data[(m - 1) * L: m * L])
+    res["loop_sample"] = m
+    res["loop_compress_wall_ms_extrapolated"] = round(tc / m * S * 1e3, 1)
+    res["loop_decompress_wall_ms_extrapolated"] = round(td / m * S * 1e3, 1)
+    res["compress_speedup"] = round(tc / m * S / min(wc), 1)
+    res["decompress_speedup"] = round(td / m * S / min(wd), 1)
+    res["loop_note"] = ("huff_enc_create + huff_enc_compress, then huff_enc_decode, one job per stream, timed over "
+                        "loop_sample streams and scaled to the batch (extrapolated, not measured over all streams)")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=10000)
     ap.add_argument("--bytes", type=int, default=16384, help="bytes per stream")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cpu-sample", type=int, default=500, help="streams built on the host for comparison")
+    ap.add_argument("--codec", action="store_true", help="also the batched codec and the per-stream loop")
+    ap.add_argument("--loop-sample", type=int, default=200, help="streams of the per-stream loop")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     ctx = H.Context(0)
@@ -66,6 +158,9 @@ def main():
     res["host_note"] = "huff_tree_from_weights + huff_tree_as_bin per stream (host/tree.cpp), 1 thread, Python loop"
     st = t.status.cpu().numpy()
     res["status_counts"] = {int(k): int(v) for k, v in zip(*np.unique(st, return_counts=True))}
+    if args.codec:
+        ctx.set_timing(False)
+        res["codec"] = [codec(ctx, kind, S, L, args.iters, args.loop_sample) for kind in ("uniform", "zipf")]
     print(json.dumps(res), flush=True)
 
 
