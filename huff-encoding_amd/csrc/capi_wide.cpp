@@ -309,4 +309,43 @@ int huff_dev_wdecompress(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_co
     });
 }
 
+// diagnostics: which wide-letter build ran, from which restart form
+uint32_t huff_diag_wide_builds(void) { return huff::dev::wide_builds(); }
+const char* huff_diag_wide_build_name(uint32_t i) { return huff::dev::wide_build_name(i); }
+uint64_t huff_diag_wide_build_launches(uint32_t i) { return huff::dev::wide_build_launches(i); }
+uint32_t huff_diag_wide_index_forms(void) { return huff::dev::wide_index_forms(); }
+const char* huff_diag_wide_index_form_name(uint32_t i) { return huff::dev::wide_index_form_name(i); }
+uint64_t huff_diag_wide_index_form_launches(uint32_t i) { return huff::dev::wide_index_form_launches(i); }
+
+int huff_wtree_diag(const huff_wtree* t, uint64_t out[HUFF_WTREE_DIAG_WORDS]) {
+    if (!t || !out) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        const huff::WideEncTables* et = nullptr;
+        const huff::WideDecTables* dt = nullptr;
+        HUFF_TRY(t->enc_tables(&et));
+        HUFF_TRY(t->dec_tables(&dt));
+        const uint32_t W = t->t.width();
+        const uint64_t v[HUFF_WTREE_DIAG_WORDS] = {
+            W,
+            et->distinct,
+            et->slots,
+            et->slot_bytes,
+            et->hash_mode,
+            et->long_codes ? 1u : 0u,
+            et->maxlen,
+            et->table.size(),
+            dt->maxdepth,
+            dt->sbits,
+            dt->stab.size(),
+            dt->w4_leaf ? 1u : 0u,
+            dt->letters.size() / W,
+            dt->bits,
+            dt->lut.size(),
+            0,
+        };
+        std::memcpy(out, v, sizeof(v));
+        return huff::Status::ok();
+    });
+}
+
 }  // extern "C"

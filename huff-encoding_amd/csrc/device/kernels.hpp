@@ -329,6 +329,21 @@ hipError_t launch_wide_bits(const WideArgs& a, hipStream_t s);
 hipError_t launch_wide_pack(const WideArgs& a, hipStream_t s);
 hipError_t launch_wide_decode(const WideDecArgs& a, hipStream_t s);       // codes > 32 bits (wide.hip)
 hipError_t launch_wide_decode_task(const WideDecArgs& a, hipStream_t s);  // codes <= 32 bits (wdecode.hip)
+// diagnostics (huffgpu_wide.h huff_diag_wide_*): the wide launchers' tables of
+// compiled builds, one enumeration over the four families in the order k_wbits
+// (20), k_wpack (32), k_wdec_task (30), k_wdecode (10), and the forms the task
+// decoder's launches read their restart entries in, with process-wide launch
+// counts. name: null past the last row.
+uint32_t wide_builds();
+const char* wide_build_name(uint32_t i);
+uint64_t wide_build_launches(uint32_t i);
+uint32_t wide_index_forms();
+const char* wide_index_form_name(uint32_t i);
+uint64_t wide_index_form_launches(uint32_t i);
+// (wdecode.hip's rows of the enumeration above, which wide.hip joins to its own)
+uint32_t wide_task_builds();
+const char* wide_task_build_name(uint32_t i);
+uint64_t wide_task_build_launches(uint32_t i);
 // build_weights_map on the device (wweights.hip). width <= 2: counts = the
 // 2^(8 width) bins (zeroed). width >= 4: an HBM table of `slots`
 // (wcount_slots of a guess of the distinct letters) keys_lo (all ones),

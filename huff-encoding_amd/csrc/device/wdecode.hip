@@ -19,6 +19,7 @@
 //
 // Roofline: HBM-bound in principle; ceil(bits/8) read + n W written + the
 // restart index (4 B per 64 letters).
+#include <atomic>
 #include <type_traits>
 
 #include "bitreader.hpp"
@@ -386,13 +387,44 @@ __global__ __launch_bounds__((LDS ? max_waves<W>() : 4) * 64) void k_wdec_task(W
     }
 }
 
+// Every compiled build of the task decoder, one row each: the kernel and its
+// name are one token sequence (WT_BUILD), so the name counted is the name of
+// the pointer launched. launch_as computes a row number and takes both from
+// the row. (The rows' order is the order the kernels have in the code object.
+// tests/test_wide_builds_host.py holds a case per reachable row.)
+using TaskKernel = void (*)(WideDecArgs);
+struct TaskBuild {
+    TaskKernel kern;
+    const char* name;
+};
+#define WT_BUILD(...) {__VA_ARGS__, #__VA_ARGS__}
+// [width][table outside LDS][level-2 entries and a refill per code, level-2 entries, level 1 only]
+#define WT_ROWS(W)                                                                                  \
+    WT_BUILD(k_wdec_task<W, true, true, true>), WT_BUILD(k_wdec_task<W, true, false, true>),        \
+    WT_BUILD(k_wdec_task<W, false, false, true>), WT_BUILD(k_wdec_task<W, true, true, false>),      \
+    WT_BUILD(k_wdec_task<W, true, false, false>), WT_BUILD(k_wdec_task<W, false, false, false>)
+static const TaskBuild kTaskBuilds[] = {WT_ROWS(1), WT_ROWS(2), WT_ROWS(4), WT_ROWS(8), WT_ROWS(16)};
+#undef WT_ROWS
+#undef WT_BUILD
+constexpr uint32_t kNumTaskBuilds = sizeof(kTaskBuilds) / sizeof(kTaskBuilds[0]);
+static_assert(kNumTaskBuilds == 30, "30 builds");
+static std::atomic<uint64_t> g_task_launches[kNumTaskBuilds];
+
+// The form a launch's tasks read their restart entries in (k_wdec_task's
+// lane_bit): the encoder's index, exact index-free points, or k_mark_lite's
+// skip marks
+static const char* const kTaskForms[] = {"chunk_start+sub_bit", "sub_abs", "sub_abs/skip"};
+constexpr uint32_t kNumTaskForms = sizeof(kTaskForms) / sizeof(kTaskForms[0]);
+static std::atomic<uint64_t> g_task_form_launches[kNumTaskForms];
+static uint32_t task_form(const WideDecArgs& a) { return !a.sub_abs ? 0u : (a.skip_packed ? 2u : 1u); }
+
 template <uint32_t W, bool LDS>
 hipError_t launch_as(const WideDecArgs& a, size_t shared, uint32_t waves, hipStream_t s) {
-    using Kern = void (*)(WideDecArgs);
     const bool two = a.max_len > a.stab_bits;
     const bool r1 = a.max_len > 16;
-    const Kern k = !two ? k_wdec_task<W, false, false, LDS>
-                        : (r1 ? k_wdec_task<W, true, true, LDS> : k_wdec_task<W, true, false, LDS>);
+    constexpr uint32_t wi = W == 1 ? 0 : W == 2 ? 1 : W == 4 ? 2 : W == 8 ? 3 : 4;
+    const uint32_t row = 6 * wi + (LDS ? 0u : 3u) + (!two ? 2u : (r1 ? 0u : 1u));
+    const TaskKernel k = kTaskBuilds[row].kern;
     const size_t lds = shared + size_t(waves) * (a.stage_bytes + row_bytes<W>());
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
@@ -406,6 +438,8 @@ hipError_t launch_as(const WideDecArgs& a, size_t shared, uint32_t waves, hipStr
     const uint64_t want = (ntasks + waves - 1) / waves;
     const uint64_t cap = uint64_t(a.cu_count ? a.cu_count : 256) * per_cu;
     const uint32_t grid = static_cast<uint32_t>(want < cap ? want : cap);
+    g_task_launches[row].fetch_add(1, std::memory_order_relaxed);
+    g_task_form_launches[task_form(a)].fetch_add(1, std::memory_order_relaxed);
     launch_k(k, dim3(grid), dim3(waves * 64), lds, s, a);
     return hipGetLastError();
 }
@@ -427,6 +461,17 @@ hipError_t by_place(const WideDecArgs& a, hipStream_t s) {
 }
 
 }  // namespace
+
+uint32_t wide_task_builds() { return kNumTaskBuilds; }
+const char* wide_task_build_name(uint32_t i) { return i < kNumTaskBuilds ? kTaskBuilds[i].name : nullptr; }
+uint64_t wide_task_build_launches(uint32_t i) {
+    return i < kNumTaskBuilds ? g_task_launches[i].load(std::memory_order_relaxed) : 0;
+}
+uint32_t wide_index_forms() { return kNumTaskForms; }
+const char* wide_index_form_name(uint32_t i) { return i < kNumTaskForms ? kTaskForms[i] : nullptr; }
+uint64_t wide_index_form_launches(uint32_t i) {
+    return i < kNumTaskForms ? g_task_form_launches[i].load(std::memory_order_relaxed) : 0;
+}
 
 hipError_t launch_wide_decode_task(const WideDecArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;

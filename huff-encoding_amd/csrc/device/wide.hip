@@ -41,6 +41,7 @@
 //            <= 32 bits: the task decoder of wdecode.hip.
 //
 // Roofline: HBM-bound. Pass 1 reads n W bytes, pass 2 n W + writes C.
+#include <atomic>
 #include <type_traits>
 
 #include "pack_emit.hpp"
@@ -670,73 +671,114 @@ inline uint32_t enc_grid(const WideArgs& a, size_t lds) {
     return need < g ? need : g;
 }
 
+// Every compiled encoder and long-code decoder build, one row each per
+// launcher family: the kernel and its name are one token sequence (W_BUILD), so
+// the name counted is the name of the pointer launched. The launchers compute
+// a row number from the facts that select a build and take both from the row.
+// (The rows' order is the order the kernels have in the code object.
+// tests/test_wide_builds_host.py holds a case per reachable row.)
+using EncKernel = void (*)(WideArgs);
+using DecKernel = void (*)(WideDecArgs);
 template <typename K>
-hipError_t allow_lds(K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024);
+struct WideBuild {
+    K kern;
+    const char* name;
+};
+#define W_BUILD(...) {__VA_ARGS__, #__VA_ARGS__}
+// pass 1: [width][short values][table outside LDS]
+#define W_BITS_ROWS(W)                                                                    \
+    W_BUILD(k_wbits<W, uint64_t, true>), W_BUILD(k_wbits<W, uint64_t, false>),            \
+    W_BUILD(k_wbits<W, uint32_t, true>), W_BUILD(k_wbits<W, uint32_t, false>)
+static const WideBuild<EncKernel> kBitsBuilds[] = {W_BITS_ROWS(1), W_BITS_ROWS(2), W_BITS_ROWS(4), W_BITS_ROWS(8),
+                                                   W_BITS_ROWS(16)};
+#undef W_BITS_ROWS
+// pass 2, letters of <= 4 bytes: [width][long values, then G = 4, 2, 1][table outside LDS]
+#define W_PACK_ROWS_G(W)                                                                  \
+    W_BUILD(k_wpack<W, uint64_t, true, 1>), W_BUILD(k_wpack<W, uint64_t, false, 1>),      \
+    W_BUILD(k_wpack<W, uint32_t, true, 4>), W_BUILD(k_wpack<W, uint32_t, false, 4>),      \
+    W_BUILD(k_wpack<W, uint32_t, true, 2>), W_BUILD(k_wpack<W, uint32_t, false, 2>),      \
+    W_BUILD(k_wpack<W, uint32_t, true, 1>), W_BUILD(k_wpack<W, uint32_t, false, 1>)
+// wider letters: [width][short values][table outside LDS]
+#define W_PACK_ROWS(W)                                                                    \
+    W_BUILD(k_wpack<W, uint64_t, true, 1>), W_BUILD(k_wpack<W, uint64_t, false, 1>),      \
+    W_BUILD(k_wpack<W, uint32_t, true, 1>), W_BUILD(k_wpack<W, uint32_t, false, 1>)
+static const WideBuild<EncKernel> kPackBuilds[] = {W_PACK_ROWS_G(1), W_PACK_ROWS_G(2), W_PACK_ROWS_G(4),
+                                                   W_PACK_ROWS(8), W_PACK_ROWS(16)};
+#undef W_PACK_ROWS_G
+#undef W_PACK_ROWS
+// the long-code decoder: [width][leaf letters outside LDS]
+static const WideBuild<DecKernel> kDecodeBuilds[] = {
+    W_BUILD(k_wdecode<uint8_t, true>),  W_BUILD(k_wdecode<uint8_t, false>),  W_BUILD(k_wdecode<uint16_t, true>),
+    W_BUILD(k_wdecode<uint16_t, false>), W_BUILD(k_wdecode<uint32_t, true>), W_BUILD(k_wdecode<uint32_t, false>),
+    W_BUILD(k_wdecode<uint64_t, true>), W_BUILD(k_wdecode<uint64_t, false>), W_BUILD(k_wdecode<U128, true>),
+    W_BUILD(k_wdecode<U128, false>),
+};
+#undef W_BUILD
+constexpr uint32_t kNumBitsBuilds = sizeof(kBitsBuilds) / sizeof(kBitsBuilds[0]);
+constexpr uint32_t kNumPackBuilds = sizeof(kPackBuilds) / sizeof(kPackBuilds[0]);
+constexpr uint32_t kNumDecodeBuilds = sizeof(kDecodeBuilds) / sizeof(kDecodeBuilds[0]);
+static_assert(kNumBitsBuilds == 20 && kNumPackBuilds == 32 && kNumDecodeBuilds == 10, "62 builds");
+static std::atomic<uint64_t> g_bits_launches[kNumBitsBuilds], g_pack_launches[kNumPackBuilds],
+    g_decode_launches[kNumDecodeBuilds];
+
+// 0 .. 4 for letters of 1, 2, 4, 8, 16 bytes
+constexpr uint32_t width_index(uint32_t w) { return w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : w == 8 ? 3u : 4u; }
+constexpr uint32_t bits_row(uint32_t w, bool long_codes, bool lds) {
+    return 4 * width_index(w) + (long_codes ? 0u : 2u) + (lds ? 0u : 1u);
+}
+// g: codes per OR pair (1 for long values and letters wider than 4 bytes)
+constexpr uint32_t pack_row(uint32_t w, bool long_codes, bool lds, int g) {
+    const uint32_t wi = width_index(w);
+    const uint32_t base = wi <= 2 ? 8 * wi : 24 + 4 * (wi - 3);
+    const uint32_t form = long_codes ? 0u : (wi > 2 ? 1u : (g == 4 ? 1u : g == 2 ? 2u : 3u));
+    return base + 2 * form + (lds ? 0u : 1u);
 }
 
-template <uint32_t W, typename V, bool LDS>
-hipError_t bits_go(const WideArgs& a, hipStream_t s) {
-    const size_t lds = wide_lds_bytes(a, false, LDS);
-    static const hipError_t attr = allow_lds(k_wbits<W, V, LDS>, 128 * 1024);
-    if (attr != hipSuccess) return attr;
-    launch_k((k_wbits<W, V, LDS>), dim3(enc_grid(a, lds)), dim3(kEncWaves * 64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <uint32_t W, typename V, bool LDS, int G>
-hipError_t pack_go(const WideArgs& a, hipStream_t s) {
-    const size_t lds = wide_lds_bytes(a, true, LDS);
-    static const hipError_t attr = allow_lds(k_wpack<W, V, LDS, G>, 128 * 1024);
-    if (attr != hipSuccess) return attr;
-    launch_k((k_wpack<W, V, LDS, G>), dim3(enc_grid(a, lds)), dim3(kEncWaves * 64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <uint32_t W, bool PACK>
-hipError_t enc_as(const WideArgs& a, hipStream_t s) {
-    if constexpr (!PACK) {
-        if (a.long_codes) return a.table_in_lds ? bits_go<W, uint64_t, true>(a, s) : bits_go<W, uint64_t, false>(a, s);
-        return a.table_in_lds ? bits_go<W, uint32_t, true>(a, s) : bits_go<W, uint32_t, false>(a, s);
-    } else {
-        if (a.long_codes)
-            return a.table_in_lds ? pack_go<W, uint64_t, true, 1>(a, s) : pack_go<W, uint64_t, false, 1>(a, s);
-        if constexpr (W <= 4) {  // groups of codes per OR pair, as pack.hip
-            if (a.max_len <= 8)
-                return a.table_in_lds ? pack_go<W, uint32_t, true, 4>(a, s) : pack_go<W, uint32_t, false, 4>(a, s);
-            if (a.max_len <= 16)
-                return a.table_in_lds ? pack_go<W, uint32_t, true, 2>(a, s) : pack_go<W, uint32_t, false, 2>(a, s);
-        }
-        return a.table_in_lds ? pack_go<W, uint32_t, true, 1>(a, s) : pack_go<W, uint32_t, false, 1>(a, s);
+// one encoder launch from row `row` of `builds`; every build may take the
+// whole LDS (set once per row)
+template <uint32_t N>
+hipError_t enc_go(const WideBuild<EncKernel> (&builds)[N], std::atomic<uint64_t> (&launches)[N], uint32_t row,
+                  bool pack_pass, const WideArgs& a, hipStream_t s) {
+    static std::atomic<int> allowed[N];  // 0: not yet, 1: done
+    const EncKernel kern = builds[row].kern;
+    if (!allowed[row].load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        allowed[row].store(1, std::memory_order_release);
     }
+    const size_t lds = wide_lds_bytes(a, pack_pass, a.table_in_lds != 0);
+    launches[row].fetch_add(1, std::memory_order_relaxed);
+    launch_k(kern, dim3(enc_grid(a, lds)), dim3(kEncWaves * 64), lds, s, a);
+    return hipGetLastError();
 }
 
 template <bool PACK>
 hipError_t by_width(const WideArgs& a, hipStream_t s) {
     if (a.nchunks == 0) return hipSuccess;
     if (a.table_in_lds && wide_lds_bytes(a, PACK, true) > kWideLdsMax) return hipErrorInvalidValue;
-    switch (a.width) {
-        case 1: return enc_as<1, PACK>(a, s);
-        case 2: return enc_as<2, PACK>(a, s);
-        case 4: return enc_as<4, PACK>(a, s);
-        case 8: return enc_as<8, PACK>(a, s);
-        case 16: return enc_as<16, PACK>(a, s);
-        default: return hipErrorInvalidValue;
+    if (a.width != 1 && a.width != 2 && a.width != 4 && a.width != 8 && a.width != 16) return hipErrorInvalidValue;
+    const bool lds = a.table_in_lds != 0, long_codes = a.long_codes != 0;
+    if constexpr (!PACK) {
+        return enc_go(kBitsBuilds, g_bits_launches, bits_row(a.width, long_codes, lds), false, a, s);
+    } else {
+        // letters of <= 4 bytes: groups of codes per OR pair, as pack.hip
+        const int g = long_codes || a.width > 4 ? 1 : (a.max_len <= 8 ? 4 : a.max_len <= 16 ? 2 : 1);
+        return enc_go(kPackBuilds, g_pack_launches, pack_row(a.width, long_codes, lds, g), true, a, s);
     }
 }
 
+// T's row pair in kDecodeBuilds
 template <typename T>
-void decode_as(const WideDecArgs& a, hipStream_t s) {
+hipError_t decode_as(const WideDecArgs& a, hipStream_t s) {
     const size_t prim = (size_t(1) << a.lut_bits) * 4;
     const size_t lw = (static_cast<size_t>(a.nleaves) * sizeof(T) + 15) / 16 * 16;
-    if (lw <= kLetterLdsMax)
-        launch_k((k_wdecode<T, true>), dim3(grid_for(dec_groups_host(a), a.cu_count, prim + lw)), dim3(kThreads),
-                           prim + lw, s, a);
-    else
-        launch_k((k_wdecode<T, false>), dim3(grid_for(dec_groups_host(a), a.cu_count, prim)), dim3(kThreads), prim,
-                           s, a);
+    const bool llds = lw <= kLetterLdsMax;
+    const uint32_t row = 2 * width_index(sizeof(T)) + (llds ? 0u : 1u);
+    const size_t lds = prim + (llds ? lw : 0);
+    g_decode_launches[row].fetch_add(1, std::memory_order_relaxed);
+    launch_k(kDecodeBuilds[row].kern, dim3(grid_for(dec_groups_host(a), a.cu_count, lds)), dim3(kThreads), lds, s, a);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -758,14 +800,34 @@ hipError_t launch_wide_pack(const WideArgs& a, hipStream_t s) { return by_width<
 hipError_t launch_wide_decode(const WideDecArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     switch (a.width) {
-        case 1: decode_as<uint8_t>(a, s); break;
-        case 2: decode_as<uint16_t>(a, s); break;
-        case 4: decode_as<uint32_t>(a, s); break;
-        case 8: decode_as<uint64_t>(a, s); break;
-        case 16: decode_as<U128>(a, s); break;
+        case 1: return decode_as<uint8_t>(a, s);
+        case 2: return decode_as<uint16_t>(a, s);
+        case 4: return decode_as<uint32_t>(a, s);
+        case 8: return decode_as<uint64_t>(a, s);
+        case 16: return decode_as<U128>(a, s);
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
+}
+
+// diagnostics: the four families' rows as one enumeration
+uint32_t wide_builds() { return kNumBitsBuilds + kNumPackBuilds + wide_task_builds() + kNumDecodeBuilds; }
+const char* wide_build_name(uint32_t i) {
+    if (i < kNumBitsBuilds) return kBitsBuilds[i].name;
+    i -= kNumBitsBuilds;
+    if (i < kNumPackBuilds) return kPackBuilds[i].name;
+    i -= kNumPackBuilds;
+    if (i < wide_task_builds()) return wide_task_build_name(i);
+    i -= wide_task_builds();
+    return i < kNumDecodeBuilds ? kDecodeBuilds[i].name : nullptr;
+}
+uint64_t wide_build_launches(uint32_t i) {
+    if (i < kNumBitsBuilds) return g_bits_launches[i].load(std::memory_order_relaxed);
+    i -= kNumBitsBuilds;
+    if (i < kNumPackBuilds) return g_pack_launches[i].load(std::memory_order_relaxed);
+    i -= kNumPackBuilds;
+    if (i < wide_task_builds()) return wide_task_build_launches(i);
+    i -= wide_task_builds();
+    return i < kNumDecodeBuilds ? g_decode_launches[i].load(std::memory_order_relaxed) : 0;
 }
 
 }  // namespace huff::dev

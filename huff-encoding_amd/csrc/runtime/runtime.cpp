@@ -83,6 +83,11 @@ namespace huff {
 //                           tables are built). test_gpu_wide
 //   HUFF_WIDE_MARK_WALK (set)  index-free wide-letter decode from exact walked
 //                           marks, not k_mark_lite's skip marks. test_gpu_wide
+//   HUFF_WIDE_CUS=<n>       the CU count the wide-letter launchers size their
+//                           persistent grids by (else the device's): with 1
+//                           every encoder wave takes several chunks and every
+//                           decoder wave several tasks at test sizes.
+//                           test_gpu_wide_builds
 //
 // The opt-in one-pass decoder's switch, HUFF_SYNC_DECODE, and its lead-ins
 // stay with decode_sync (below), to leave with it. Diagnostics stay beside
@@ -117,6 +122,12 @@ bool l2_table_disabled() { return std::getenv("HUFF_NO_L2") != nullptr; }
 bool l2_sparse_forced() { return std::getenv("HUFF_L2_SPARSE") != nullptr; }
 
 bool wide_mark_walk() { return std::getenv("HUFF_WIDE_MARK_WALK") != nullptr; }
+
+uint32_t wide_cu_count(uint32_t device_cus) {
+    const char* e = std::getenv("HUFF_WIDE_CUS");
+    const long v = e ? std::atol(e) : 0;
+    return v >= 1 && v <= 65535 ? static_cast<uint32_t>(v) : device_cus;
+}
 
 #ifdef HUFF_STAMPS
 // Timing builds only (tools/build_variant.sh -DHUFF_STAMPS): per-wave phase

@@ -88,6 +88,8 @@ bool l2_table_disabled();
 bool l2_sparse_forced();
 // HUFF_WIDE_MARK_WALK: index-free wide-letter decode from exact walked marks
 bool wide_mark_walk();
+// HUFF_WIDE_CUS=<n>: the CU count of the wide launchers' grids (else device_cus)
+uint32_t wide_cu_count(uint32_t device_cus);
 
 // HUFF_HOST_TRACE: when huff_enc::pack finished its bit count, started and
 // returned from the byte-map launch (this thread's last pack)

@@ -79,7 +79,7 @@ huff::dev::WideArgs huff_wenc::enc_args(bool pack_pass) const {
     a.long_codes = et->long_codes;
     a.max_len = et->maxlen;
     a.nchunks = nchunks;
-    a.cu_count = static_cast<uint32_t>(ctx->cu_count);
+    a.cu_count = huff::wide_cu_count(static_cast<uint32_t>(ctx->cu_count));
     a.stage_words = huff::dev::wide_stage_words(width, et->maxlen);
     a.table_in_lds = huff::dev::wide_lds_bytes(a, pack_pass, true) <= huff::dev::kWideLdsMax;
     return a;
@@ -178,7 +178,7 @@ Status huff_wenc::decode(const huff_wtree* t, const uint8_t* d_comp, uint64_t co
     a.sub_abs = sub_abs;
     a.skip_packed = skip_packed ? 1u : 0u;
     a.nchunks = nchunks;
-    a.cu_count = static_cast<uint32_t>(ctx->cu_count);
+    a.cu_count = huff::wide_cu_count(static_cast<uint32_t>(ctx->cu_count));
     a.n = n;
     a.out = d_out;
     a.end_bit = comp_bytes * 8;  // bounds the last task's staged range

@@ -161,6 +161,13 @@ SIGNATURES = [
     ("huff_wenc_pack", i, [vp, vp, vp, sz, vp]),
     ("huff_wenc_decode", i, [vp, vp, vp, vp]),
     ("huff_dev_wdecompress", i, [vp, vp, vp, sz, C.c_uint8, vp, sz, szp]),
+    ("huff_diag_wide_builds", C.c_uint32, []),
+    ("huff_diag_wide_build_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_wide_build_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_diag_wide_index_forms", C.c_uint32, []),
+    ("huff_diag_wide_index_form_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_wide_index_form_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_wtree_diag", i, [vp, u64p]),
 ]
 
 _lib = None
@@ -194,6 +201,21 @@ def decode_index_form_launches() -> dict:
     L = load()
     return {L.huff_diag_decode_index_form_name(k).decode(): L.huff_diag_decode_index_form_launches(k)
             for k in range(L.huff_diag_decode_index_forms())}
+
+
+def wide_build_launches() -> dict:
+    """{build name: launches so far} of the wide-letter kernels' compiled builds
+    (huff_diag_wide_build_*): k_wbits, k_wpack, k_wdec_task, k_wdecode rows, in that order"""
+    L = load()
+    return {L.huff_diag_wide_build_name(k).decode(): L.huff_diag_wide_build_launches(k)
+            for k in range(L.huff_diag_wide_builds())}
+
+
+def wide_index_form_launches() -> dict:
+    """{restart form: k_wdec_task launches so far} (huff_diag_wide_index_form_*)"""
+    L = load()
+    return {L.huff_diag_wide_index_form_name(k).decode(): L.huff_diag_wide_index_form_launches(k)
+            for k in range(L.huff_diag_wide_index_forms())}
 
 
 def last_error() -> str:

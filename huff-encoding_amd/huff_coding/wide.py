@@ -154,6 +154,15 @@ class WideTree:
         vals = self.ltype.values(letters)
         return {v: format(int(c), f"0{int(l)}b") for v, c, l in zip(vals, code, ln)}
 
+    DIAG_FIELDS = ("width", "distinct", "slots", "slot_bytes", "hash_mode", "long_codes", "maxlen", "table_bytes",
+                   "maxdepth", "sbits", "stab_bytes", "w4_leaf", "leaves", "lut_bits", "lut_entries")
+
+    def diag(self) -> Dict[str, int]:
+        """the geometry of the tree's device tables (huff_wtree_diag): host only, no GPU"""
+        out = (C.c_uint64 * 16)()
+        _check(load().huff_wtree_diag(self.h, out))
+        return {k: int(out[i]) for i, k in enumerate(self.DIAG_FIELDS)}
+
     def as_bin(self) -> str:
         """tree_inner.rs:632-668 as a '0'/'1' string"""
         n = C.c_size_t()

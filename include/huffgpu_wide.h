@@ -112,6 +112,38 @@ int huff_wenc_decode(huff_wenc* e, const huff_wtree* t, const uint8_t* d_comp, u
 int huff_dev_wdecompress(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
                          uint8_t padding, void* d_out, size_t out_cap_letters, size_t* n_out);
 
+/* ---------------- diagnostics (not reference functions) ------------------ */
+/* The wide launchers take their kernels from tables of compiled builds: 20
+ * k_wbits (pass 1), 32 k_wpack (pass 2), 30 k_wdec_task (codes <= 32 bits)
+ * and 10 k_wdecode (longer codes) rows, enumerated in that order.
+ * huff_diag_wide_builds() rows; the name of row i is the kernel's template
+ * instantiation as the source spells it (NULL past the last row), and the
+ * count is the number of launches of that row by this process so far. */
+uint32_t huff_diag_wide_builds(void);
+const char* huff_diag_wide_build_name(uint32_t i);
+uint64_t huff_diag_wide_build_launches(uint32_t i);
+/* the forms a k_wdec_task launch reads its restart entries in:
+ * "chunk_start+sub_bit" (the job's index), "sub_abs" (index-free, walked exact
+ * points: HUFF_WIDE_MARK_WALK) and "sub_abs/skip" (index-free, skip marks) */
+uint32_t huff_diag_wide_index_forms(void);
+const char* huff_diag_wide_index_form_name(uint32_t i);
+uint64_t huff_diag_wide_index_form_launches(uint32_t i);
+/* The geometry of a tree's device tables, computed on the host (no context,
+ * no GPU): the facts the launchers select a build by, not the build.
+ * out[0] letter width in bytes          out[8]  deepest code (decoder tables)
+ * out[1] distinct letters with a code   out[9]  task table: level-1 index bits
+ * out[2] encoder hash table slots       out[10] task table bytes (0: none, the
+ * out[3] bytes per slot                         long-code decoder decodes)
+ * out[4] hash form (0 generic,          out[11] 1: 4-byte letters as leaf indices
+ *        1 narrow, 2 direct)            out[12] leaves
+ * out[5] 1: u64 values (codes > 27 bits) out[13] long-code table: primary index bits
+ * out[6] longest code (encoder tables)  out[14] long-code table entries
+ * out[7] encoder table bytes            out[15] 0
+ * HUFF_E_CODE_TOO_LONG where the encoder (> 56 bits) or decoder (> 57 bits)
+ * tables refuse the tree. */
+#define HUFF_WTREE_DIAG_WORDS 16
+int huff_wtree_diag(const huff_wtree* t, uint64_t out[HUFF_WTREE_DIAG_WORDS]);
+
 #ifdef __cplusplus
 }
 #endif
