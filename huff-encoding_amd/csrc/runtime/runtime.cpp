@@ -2,10 +2,8 @@
 #include "runtime.hpp"
 
 #include <algorithm>
-#include <cmath>
 #include <cctype>
 #include <chrono>
-#include <numeric>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +15,14 @@ namespace {
 std::atomic<uint64_t> g_tree_ids{1};
 
 }  // namespace
+
+// host/dectables.hpp builds the tables the kernels read, to its own copies of
+// their constants
+static_assert(huff::kLutPtr == huff::dev::kLutPtr, "host/dectables.hpp mirrors dev::kLutPtr");
+static_assert(huff::kLutMaxBits == huff::dev::kLutMaxBits, "host/dectables.hpp mirrors dev::kLutMaxBits");
+static_assert(huff::kSsMaxBits == huff::dev::kSsMaxBits, "host/dectables.hpp mirrors dev::kSsMaxBits");
+static_assert(huff::kSsSlow == huff::dev::kSsSlow, "host/dectables.hpp mirrors dev::kSsSlow");
+static_assert(huff::kLongMaxLen == huff::dev::kLongMaxLen, "host/dectables.hpp mirrors dev::kLongMaxLen");
 
 #define HIP_TRY(expr) HIP_TRY_RT(expr)
 
@@ -47,7 +53,7 @@ huff::Status huff_tree::dec_tables(const huff::DecTables** out) const {
     std::lock_guard<std::mutex> g(m);
     if (!dec) {
         auto d = std::make_unique<huff::DecTables>();
-        HUFF_TRY(huff::build_dec_tables(t, *d));
+        HUFF_TRY(huff::build_dec_tables(t, huff::l2_sparse_forced(), *d));
         dec = std::move(d);
     }
     *out = dec.get();
@@ -89,9 +95,7 @@ namespace huff {
 //                           decoder wave several tasks at test sizes.
 //                           test_gpu_wide_builds
 //
-// The opt-in one-pass decoder's switch, HUFF_SYNC_DECODE, and its lead-ins
-// stay with decode_sync (below), to leave with it. Diagnostics stay beside
-// the code they report on: HUFF_FIX_STATS (below),
+// Diagnostics stay beside the code they report on: HUFF_FIX_STATS (below),
 // HUFF_TIME_FENCE / HUFF_TIME_MARKERS (huff_ctx::timed), HUFF_HOST_TRACE
 // (capi.cpp), HUFF_FILE_* (filepath.cpp).
 bool fixed8_disabled() {
@@ -143,6 +147,22 @@ uint64_t* stamp_region(int r) {
 }
 #endif
 
+// the k_decode_fixed part of DecodeArgs: the tables uploaded to d_lut, and
+// the stage and refill choices for a stream of `bits` bits holding n letters
+static void fill_fixed_decode(dev::DecodeArgs& a, const huff_ctx* ctx, const DecTables* dt, uint64_t bits, uint64_t n) {
+    a.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
+    a.lut_bits = dt->bits;
+    a.lut_words = static_cast<uint32_t>(dt->lut.size());
+    a.max_len = dt->maxdepth;
+    a.stab = ctx->lut_u16(dt->soff);
+    a.stab_bits = dt->sbits;
+    a.cu_count = static_cast<uint32_t>(ctx->cu_count);
+    a.pad_stage = dev::fixed_decode_pad(bits, n);
+    a.small_stage = small_stage_enabled() && dev::fixed_decode_small(bits, n);
+    a.refill_cap = decode_refill_cap();
+    a.n = n;
+}
+
 // a checked k_decode_fixed launch: zero the mismatch record before, read it
 // after (a host wait: test builds only)
 Status run_checked_decode(huff_ctx* ctx, dev::DecodeArgs& a, const std::function<hipError_t()>& launch) {
@@ -163,247 +183,6 @@ Status run_checked_decode(huff_ctx* ctx, dev::DecodeArgs& a, const std::function
                        "successor's restart point; first: task " + std::to_string(e[1]) + " lane " +
                        std::to_string(e[2]) + " ended at bit " + std::to_string(got) + ", expected " +
                        std::to_string(want));
-}
-
-// The decode tables are built once per tree, on the host, between pass 1 and
-// the decode. Each used to walk the tree bit by bit for every one of its 2^K
-// windows (~0.2 ms uniform, ~0.45 ms Zipf on this container's CPU), which at
-// 128 MiB per rank outlasted the pack it hides behind; they are now filled
-// from the tree's top K levels once (O(2^K + nodes)) and the walk table by a
-// recurrence over window prefixes.
-
-// the top K levels of the tree (K = sbits): entry i of `single` is the first
-// code of the K-bit window i (MSB first) as decompress walks it
-// (comp.rs:487-519): len | letter << 8, or kSsSlow when the window ends on an
-// internal node (listed in `slow` with that node, ascending window order)
-static void top_levels(const HuffTree& t, uint32_t K, uint16_t* single,
-                       std::vector<std::pair<uint32_t, int32_t>>* slow) {
-    const auto& nodes = t.nodes();
-    const uint32_t n = 1u << K;
-    if (t.root_is_leaf()) {  // every bit decodes the root letter (comp.rs:506-509)
-        const uint16_t e = static_cast<uint16_t>(1u | (static_cast<uint32_t>(nodes[t.root()].letter) << 8));
-        for (uint32_t i = 0; i < n; ++i) single[i] = e;
-        return;
-    }
-    struct F {
-        int32_t node;
-        uint32_t depth, path;
-    };
-    std::vector<F> st{{t.root(), 0, 0}};
-    while (!st.empty()) {
-        const F f = st.back();
-        st.pop_back();
-        const HuffNode& nd = nodes[f.node];
-        if (f.depth && nd.is_leaf) {
-            const uint16_t e = static_cast<uint16_t>(f.depth | (static_cast<uint32_t>(nd.letter) << 8));
-            const uint32_t lo = f.path << (K - f.depth), hi = (f.path + 1) << (K - f.depth);
-            for (uint32_t i = lo; i < hi; ++i) single[i] = e;
-        } else if (f.depth == K) {
-            single[f.path] = static_cast<uint16_t>(dev::kSsSlow);
-            if (slow) slow->push_back({f.path, f.node});
-        } else {  // right first on the stack: windows come out in ascending order
-            st.push_back({nd.right, f.depth + 1, (f.path << 1) | 1});
-            st.push_back({nd.left, f.depth + 1, f.path << 1});
-        }
-    }
-}
-
-// entry i of the single-symbol table: the first code of the sbits-bit window i
-static void build_single_table(const HuffTree& t, uint32_t sbits, DecTables& out,
-                               std::vector<std::pair<uint32_t, int32_t>>* slow = nullptr) {
-    const uint32_t n = 1u << sbits;
-    out.sbits = sbits;
-    out.soff = static_cast<uint32_t>(out.lut.size());
-    out.lut.resize(out.lut.size() + (n + 1) / 2, 0);
-    top_levels(t, sbits, reinterpret_cast<uint16_t*>(out.lut.data() + out.soff), slow);
-}
-
-// entry i of the walk table: every complete code of the sbits-bit window i
-// (bits used, count, the first code's length), for walking a stream without
-// its letters. Over the windows' suffixes: the m-bit string v holds its
-// first code (length l <= m, from the single table at v << (K - m)) and then
-// the complete codes of its last m - l bits, so (count, used) of every
-// m-bit string follow from those of shorter ones, m = 1 .. K.
-static void build_walk_table(const HuffTree& t, uint32_t sbits, DecTables& out) {
-    (void)t;
-    const uint32_t K = sbits, n = 1u << K;
-    out.woff = static_cast<uint32_t>(out.lut.size());
-    out.lut.resize(out.lut.size() + (n + 1) / 2, 0);
-    const uint16_t* single = reinterpret_cast<const uint16_t*>(out.lut.data() + out.soff);
-    uint16_t* w = reinterpret_cast<uint16_t*>(out.lut.data() + out.woff);
-    // cu[(1 << m) + v] = count | used << 8 of the m-bit string v
-    std::vector<uint16_t> cu(size_t(2) << K, 0);
-    for (uint32_t m = 1; m <= K; ++m) {
-        uint16_t* row = cu.data() + (size_t(1) << m);
-        for (uint32_t v = 0; v < (1u << m); ++v) {
-            const uint32_t e = single[v << (K - m)];
-            const uint32_t l = e & 63u;
-            if ((e & dev::kSsSlow) || l > m) continue;  // no complete code
-            const uint32_t r = cu[(size_t(1) << (m - l)) + (v & ((1u << (m - l)) - 1))];
-            row[v] = static_cast<uint16_t>(((r & 0xFFu) + 1) | (((r >> 8) + l) << 8));
-            if (m == K)
-                w[v] = static_cast<uint16_t>(l | (((r >> 8) + l) << 8) | (((r & 0xFFu) + 1) << 12));
-        }
-    }
-    for (uint32_t v = 0; v < n; ++v)
-        if ((cu[n + v] & 0xFFu) == 0) w[v] = static_cast<uint16_t>(dev::kSsSlow);
-}
-
-// The sync kernels' level-2 length table (DecTables::l2off): for every
-// sbits-bit window whose first code is longer, the lengths of the codes below
-// that node, indexed by exactly the E bits its deepest leaf needs; the slow
-// entries of the single-symbol and walk tables get the descriptor index. Only
-// the code lengths matter to the speculative pass and the marks, so a window
-// that once took two dependent global reads (the 8-bit secondary tables) takes
-// two LDS reads. Skipped past kL2MaxBytes (the LDS beside the stage) or for
-// codes > 32 bits.
-// Uniform form (DecTables::l2E) when it fits: every slow window gets 2^Emax
-// lengths (Emax = the deepest leaf below any of them), so a slow step reads
-// one length at index << Emax | next bits instead of a descriptor and then a
-// length (two dependent LDS reads).
-static void build_len_l2(const HuffTree& t, const std::vector<std::pair<uint32_t, int32_t>>& slow_nodes,
-                         DecTables& out) {
-    constexpr size_t kL2MaxBytes = 24 * 1024;
-    constexpr uint32_t kMaxDesc = 1u << 15;
-    const uint32_t K = out.sbits;
-    if (t.root_is_leaf() || out.maxdepth <= K || out.maxdepth > 32) return;
-    const auto& nodes = t.nodes();
-    struct Slow {
-        uint32_t window;
-        int32_t node;
-        uint32_t E;  // the deepest leaf below node, relative to it
-    };
-    std::vector<Slow> slow;
-    uint32_t Emax = 0;
-    size_t desc_bytes = 0;
-    for (const auto& [i, x] : slow_nodes) {
-        uint32_t E = 0;
-        std::vector<std::pair<int32_t, uint32_t>> st{{x, 0}};
-        while (!st.empty()) {
-            auto [y, d] = st.back();
-            st.pop_back();
-            if (nodes[y].is_leaf) {
-                E = std::max(E, d);
-            } else {
-                st.push_back({nodes[y].left, d + 1});
-                st.push_back({nodes[y].right, d + 1});
-            }
-        }
-        if (slow.size() >= kMaxDesc || K + E > 32) return;
-        slow.push_back({i, x, E});
-        Emax = std::max(Emax, E);
-        desc_bytes += 4 + (size_t(1) << E);
-    }
-    if (slow.empty()) return;
-    const bool uniform = (slow.size() << Emax) <= kL2MaxBytes;
-    if (!uniform && desc_bytes > kL2MaxBytes) return;
-    // the length of the code below `x` whose next E bits are j
-    auto len_below = [&](int32_t x, uint32_t E, uint32_t j) {
-        int32_t y = x;
-        for (uint32_t p = 0; p < E; ++p) {
-            y = ((j >> (E - 1 - p)) & 1u) ? nodes[y].right : nodes[y].left;
-            if (nodes[y].is_leaf) return static_cast<uint8_t>(K + p + 1);
-        }
-        return static_cast<uint8_t>(K + E);
-    };
-    std::vector<uint8_t> b;
-    if (uniform) {
-        out.l2E = Emax;
-        out.l2dense = slow.size() * 64 > (size_t(1) << K) && !l2_sparse_forced();
-        b.resize(slow.size() << Emax);
-        for (size_t s = 0; s < slow.size(); ++s)
-            for (uint32_t j = 0; j < (1u << Emax); ++j) b[(s << Emax) + j] = len_below(slow[s].node, Emax, j);
-    } else {  // descriptors (byte offset << 5 | E), then each window's 2^E lengths
-        out.l2E = 0;
-        b.resize(slow.size() * 4);
-        for (size_t s = 0; s < slow.size(); ++s) {
-            const uint32_t d = static_cast<uint32_t>((b.size() << 5) | slow[s].E);
-            std::memcpy(&b[s * 4], &d, 4);
-            for (uint32_t j = 0; j < (1u << slow[s].E); ++j) b.push_back(len_below(slow[s].node, slow[s].E, j));
-        }
-    }
-    out.l2off = static_cast<uint32_t>(out.lut.size());
-    out.l2words = static_cast<uint32_t>((b.size() + 15) / 16 * 4);
-    out.lut.resize(out.lut.size() + out.l2words, 0);
-    std::memcpy(out.lut.data() + out.l2off, b.data(), b.size());
-    std::vector<std::pair<uint32_t, uint32_t>> slow_ix;  // (window, index)
-    for (size_t s = 0; s < slow.size(); ++s) slow_ix.push_back({slow[s].window, static_cast<uint32_t>(s)});
-    uint16_t* s = reinterpret_cast<uint16_t*>(out.lut.data() + out.soff);
-    uint16_t* w = reinterpret_cast<uint16_t*>(out.lut.data() + out.woff);
-    for (auto [i, d] : slow_ix) {
-        const uint16_t e = static_cast<uint16_t>(dev::kSsSlow | (d & 0x7Fu) | ((d >> 7) << 8));
-        s[i] = e;
-        w[i] = e;
-    }
-}
-
-Status build_dec_tables(const HuffTree& t, DecTables& out) {
-    const auto& nodes = t.nodes();
-    out.lut.clear();
-    out.l2off = out.l2words = out.l2E = 0;
-    out.l2dense = false;
-    if (t.root_is_leaf()) {  // every bit decodes the root letter (comp.rs:506-509)
-        out.bits = 1;
-        out.maxdepth = 1;
-        const uint32_t e = (1u << 8) | nodes[t.root()].letter;
-        out.lut = {e, e};
-        build_single_table(t, 1, out);
-        build_walk_table(t, 1, out);
-        return Status::ok();
-    }
-    uint32_t mind = 0, maxd = 0;  // maxd > dev::kLongMaxLen: the deep kernels (deep.hip)
-    t.depth_range(&mind, &maxd);
-    out.maxdepth = maxd;
-    out.all8 = (mind == 8 && maxd == 8);
-    out.bits = std::min<uint32_t>(maxd, dev::kLutMaxBits - 1);  // 11 bits: 8 KiB of LDS
-    if (out.bits < 1) out.bits = 1;
-    out.lut.assign(1u << out.bits, 0);
-
-    // fill the table rooted at internal node `x` (depth d0, tb index bits)
-    struct Job {
-        int32_t x;
-        uint32_t d0, tb, base;
-    };
-    std::vector<Job> jobs{{t.root(), 0, out.bits, 0}};
-    while (!jobs.empty()) {
-        Job j = jobs.back();
-        jobs.pop_back();
-        struct F {
-            int32_t node;
-            uint32_t r;
-            uint32_t path;
-        };
-        std::vector<F> st{{nodes[j.x].right, 1, 1}, {nodes[j.x].left, 1, 0}};
-        while (!st.empty()) {
-            F f = st.back();
-            st.pop_back();
-            const HuffNode& nd = nodes[f.node];
-            if (nd.is_leaf) {
-                const uint32_t e = ((j.d0 + f.r) << 8) | nd.letter;
-                const uint32_t lo = f.path << (j.tb - f.r), hi = (f.path + 1) << (j.tb - f.r);
-                for (uint32_t i = lo; i < hi; ++i) out.lut[j.base + i] = e;
-            } else if (f.r == j.tb) {
-                const uint32_t sub = static_cast<uint32_t>(out.lut.size());
-                out.lut.resize(out.lut.size() + 256, 0);
-                out.lut[j.base + f.path] = dev::kLutPtr | sub;
-                jobs.push_back({f.node, j.d0 + j.tb, 8, sub});
-            } else {
-                st.push_back({nd.right, f.r + 1, (f.path << 1) | 1});
-                st.push_back({nd.left, f.r + 1, f.path << 1});
-            }
-        }
-    }
-    std::vector<std::pair<uint32_t, int32_t>> slow;  // the single table's slow windows and their nodes
-    build_single_table(t, std::min<uint32_t>(maxd, dev::kSsMaxBits), out, &slow);
-    if (slow.empty()) {
-        const uint16_t* st = reinterpret_cast<const uint16_t*>(out.lut.data() + out.soff);
-        uint64_t sum = 0;
-        for (uint32_t i = 0; i < (1u << out.sbits); ++i) sum += st[i] & 63u;
-        out.kraft_bits = static_cast<double>(sum) / static_cast<double>(1u << out.sbits);
-    }
-    build_walk_table(t, out.sbits, out);
-    build_len_l2(t, slow, out);
-    return Status::ok();
 }
 
 }  // namespace huff
@@ -606,43 +385,49 @@ private:
     uint64_t spin_ = 0;
 };
 
-huff::Status huff_enc::launch_publish(uint64_t* tag) {
-    HUFF_TRY(ctx->pin_w.ensure(256 * 8));
-    if (!ctx->pin_w_dev) {
-        std::memset(ctx->pin_w.p, 0, 256 * 8);
-        HIP_TRY(hipHostGetDevicePointer(&ctx->pin_w_dev, ctx->pin_w.p, 0));
+huff::Status TaggedWords::arm(size_t words, huff::dev::HistDone* done) {
+    HUFF_TRY(pin.ensure(words * 8));
+    if (!dev) {
+        std::memset(pin.p, 0, words * 8);
+        HIP_TRY(hipHostGetDevicePointer(&dev, pin.p, 0));
     }
-    huff::dev::HistDone done;
-    done.host = static_cast<unsigned long long*>(ctx->pin_w_dev);
-    ctx->hist_seq = (ctx->hist_seq % 0xFFFF) + 1;  // 1..65535: never the zeroed buffer's tag
-    done.tag = ctx->hist_seq;
-    HUFF_TRY(ctx->timed("hist", [&] {
-        return huff::dev::launch_hist(d_in, 0, n, nchunks, static_cast<uint32_t*>(chunk_hist.p),
-                                      static_cast<unsigned long long*>(gw.p), ctx->stream, done);
-    }));
-    *tag = done.tag;
+    seq = (seq % 0xFFFF) + 1;
+    done->host = static_cast<unsigned long long*>(dev);
+    done->tag = seq;
     return huff::Status::ok();
 }
 
-huff::Status huff_enc::wait_weights(uint64_t tag) {
-    // every word carries the launch's tag once written (k_rows_publish)
-    const uint64_t* hw = static_cast<const uint64_t*>(ctx->pin_w.p);
-    hipStream_t s = ctx->stream;
-    int b = 0;
+huff::Status TaggedWords::wait(hipStream_t s, uint64_t tag, uint64_t* out, size_t words, const char* what) {
+    // every word carries the launch's tag once written. (A fault in a kernel
+    // before the publishing one stops the stream before it publishes: the
+    // liveness check reports it.)
+    const uint64_t* hw = static_cast<const uint64_t*>(pin.p);
+    size_t b = 0;
     SpinWait sw;
-    while (b < 256) {
+    while (b < words) {
         const uint64_t v = __atomic_load_n(&hw[b], __ATOMIC_ACQUIRE);
         if ((v >> 48) == tag) {
-            w[b++] = v & ((1ull << 48) - 1);
+            out[b++] = v & ((1ull << 48) - 1);
             continue;
         }
         if (sw.check_due()) {
             const hipError_t q = hipStreamQuery(s);
             if (q == hipSuccess && (__atomic_load_n(&hw[b], __ATOMIC_ACQUIRE) >> 48) != tag)
-                return huff::Status::err(HUFF_E_HIP, "pass 1 finished without publishing its weights");
+                return huff::Status::err(HUFF_E_HIP, what);
             if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
         }
     }
+    return huff::Status::ok();
+}
+
+huff::Status huff_enc::launch_publish(uint64_t* tag) {
+    huff::dev::HistDone done;
+    HUFF_TRY(ctx->weights.arm(256, &done));
+    HUFF_TRY(ctx->timed("hist", [&] {
+        return huff::dev::launch_hist(d_in, 0, n, nchunks, static_cast<uint32_t*>(chunk_hist.p),
+                                      static_cast<unsigned long long*>(gw.p), ctx->stream, done);
+    }));
+    *tag = done.tag;
     return huff::Status::ok();
 }
 
@@ -681,7 +466,7 @@ huff::Status huff_enc::hist() {
     } else {
         HUFF_TRY(launch_publish(&tag));
     }
-    HUFF_TRY(wait_weights(tag));
+    HUFF_TRY(ctx->weights.wait(ctx->stream, tag, w, 256, "pass 1 finished without publishing its weights"));
     have_hist = true;
     packed = false;
     return huff::Status::ok();
@@ -781,7 +566,7 @@ huff::Status huff_enc::pack(const huff_tree* t, uint64_t base, const uint8_t* pr
     uint64_t tb = 0;
     HUFF_TRY(bits(t, &tb));
     ps.bits = std::chrono::steady_clock::now();
-    compact_index = false;  // set by the general pack below when it writes the compact index
+    compact_index = false;  // (also when the pack is refused below)
     const uint64_t need = ((base & 7) + tb + 7) / 8;
     if (total) *total = tb;
     if (need > out_cap) return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
@@ -811,12 +596,7 @@ huff::Status huff_enc::pack(const huff_tree* t, uint64_t base, const uint8_t* pr
             ps.launch = std::chrono::steady_clock::now();
             HUFF_TRY(ctx->timed("pack", [&] { return huff::dev::launch_bytemap(m, s); }));
             ps.launched = std::chrono::steady_clock::now();
-            packed = true;
-            index_pending = true;  // arithmetic: written only if a consumer needs it
-            packed_tree_id = t->id;
-            remember_tree(t);
-            bit_base = base;
-            total_bits = tb;
+            set_packed(t, base, tb, true, false);  // the index is arithmetic: written only if a consumer needs it
             return huff::Status::ok();
         }
     }
@@ -862,12 +642,7 @@ huff::Status huff_enc::pack(const huff_tree* t, uint64_t base, const uint8_t* pr
         d.out = d_out;
         d.sub_bit = static_cast<uint32_t*>(sub_bit.p);
         HUFF_TRY(ctx->timed("pack", [&] { return huff::dev::launch_pack_deep(d, s); }));
-        packed = true;
-        index_pending = false;
-        packed_tree_id = t->id;
-        remember_tree(t);
-        bit_base = base;
-        total_bits = tb;
+        set_packed(t, base, tb, false, false);
         return huff::Status::ok();
     }
     huff::dev::PackArgs a{};
@@ -902,14 +677,18 @@ huff::Status huff_enc::pack(const huff_tree* t, uint64_t base, const uint8_t* pr
     const uint32_t wpg = huff::dev::pack_waves_per_group(long_codes);
     a.grid = std::max<uint32_t>(1, std::min<uint32_t>((nchunks + wpg - 1) / wpg, ctx->cu_count * per_cu));
     HUFF_TRY(ctx->timed("pack", [&] { return huff::dev::launch_pack(long_codes, a, s); }));
+    set_packed(t, base, tb, false, compact);
+    return huff::Status::ok();
+}
+
+void huff_enc::set_packed(const huff_tree* t, uint64_t base, uint64_t bits, bool pending, bool compact) {
     packed = true;
-    index_pending = false;
+    index_pending = pending;
     compact_index = compact;
     packed_tree_id = t->id;
     remember_tree(t);
     bit_base = base;
-    total_bits = tb;
-    return huff::Status::ok();
+    total_bits = bits;
 }
 
 huff::Status huff_enc::ensure_index() {
@@ -955,29 +734,21 @@ huff::Status huff_enc::decode(const huff_tree* t, const uint8_t* d_comp, uint64_
     HUFF_TRY(ctx->upload_dec_tables(t, &dt));
     HUFF_TRY(ensure_index());
     huff::dev::DecodeArgs a{};
+    a.comp = d_comp;
+    a.comp_bytes = comp_bytes;
+    a.chunk_start = static_cast<const uint64_t*>(chunk_start.p);
+    a.sub_bit = static_cast<const uint32_t*>(sub_bit.p);
+    a.nchunks = nchunks;
     if (dt->maxdepth > huff::dev::kLongMaxLen) {  // deep codes (deep.hip)
-        a.comp = d_comp;
-        a.comp_bytes = comp_bytes;
         a.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
         a.lut_bits = dt->bits;
-        a.chunk_start = static_cast<const uint64_t*>(chunk_start.p);
-        a.sub_bit = static_cast<const uint32_t*>(sub_bit.p);
-        a.nchunks = nchunks;
         a.n = n;
         a.out = d_out;
         HUFF_TRY(ctx->timed("decode", [&] { return huff::dev::launch_decode_deep(a, ctx->stream); }));
         HIP_TRY(hipEventRecord(ctx->lut_free, ctx->stream));
         return huff::Status::ok();
     }
-    a.comp = d_comp;
-    a.comp_bytes = comp_bytes;
-    a.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
-    a.lut_bits = dt->bits;
-    a.lut_words = static_cast<uint32_t>(dt->lut.size());
-    a.chunk_start = static_cast<const uint64_t*>(chunk_start.p);
-    a.sub_bit = static_cast<const uint32_t*>(sub_bit.p);
-    a.nchunks = nchunks;
-    a.max_len = dt->maxdepth;
+    huff::fill_fixed_decode(a, ctx, dt, total_bits, n);
     // codes <= 32 bits: the fixed-count decoder (decode_wave.hip,
     // k_decode_fixed; the round-1 ring, multi-symbol and single-symbol
     // decoders were 1.2-1.9x slower and are retired); HUFF_DEC_VARIANT=11
@@ -1001,13 +772,6 @@ huff::Status huff_enc::decode(const huff_tree* t, const uint8_t* d_comp, uint64_
         HUFF_TRY(ctx->d_align.ensure(n + 64));
         dst = static_cast<uint8_t*>(ctx->d_align.p);
     }
-    a.cu_count = static_cast<uint32_t>(ctx->cu_count);
-    a.pad_stage = huff::dev::fixed_decode_pad(total_bits, n);
-    a.small_stage = huff::small_stage_enabled() && huff::dev::fixed_decode_small(total_bits, n);
-    a.refill_cap = huff::decode_refill_cap();
-    a.stab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->soff);
-    a.stab_bits = dt->sbits;
-    a.n = n;
     a.out = dst;
 #ifdef HUFF_STAMPS
     a.stamps = huff::stamp_region(2);
@@ -1292,9 +1056,9 @@ Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes,
     a.x = static_cast<uint64_t*>(st.x0.p);
     a.c = static_cast<uint64_t*>(st.c.p);
     a.max_len = dt->maxdepth;
-    a.stab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->soff);
+    a.stab = ctx->lut_u16(dt->soff);
     a.stab_bits = dt->sbits;
-    a.wtab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->woff);
+    a.wtab = ctx->lut_u16(dt->woff);
     if (dt->l2words && !l2_table_disabled()) {  // else the global secondary tables
         a.l2 = static_cast<const uint32_t*>(ctx->d_lut.p) + dt->l2off;
         a.l2_words = dt->l2words;
@@ -1338,15 +1102,8 @@ Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes,
     // the total goes from the scan's last kernel straight to pinned host
     // memory, tagged; the host polls it (a copy and a stream
     // synchronisation here cost ~40 us between the sync and the decode)
-    HUFF_TRY(ctx->pin_total.ensure(8));
-    if (!ctx->pin_total_dev) {
-        std::memset(ctx->pin_total.p, 0, 8);
-        HIP_TRY(hipHostGetDevicePointer(&ctx->pin_total_dev, ctx->pin_total.p, 0));
-    }
     dev::HistDone done;
-    done.host = static_cast<unsigned long long*>(ctx->pin_total_dev);
-    ctx->total_seq = (ctx->total_seq % 0xFFFF) + 1;  // 1..65535: never the zeroed word's tag
-    done.tag = ctx->total_seq;
+    HUFF_TRY(ctx->total.arm(1, &done));
     if (st.block_off) {
         HIP_TRY(dev::launch_scan(static_cast<const uint64_t*>(st.wtot.p), static_cast<uint32_t>(nwg), 0,
                                  static_cast<uint64_t*>(st.woff.p), static_cast<uint64_t*>(st.tsum.p), strm, done));
@@ -1356,34 +1113,19 @@ Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes,
                                  static_cast<uint64_t*>(st.off.p), static_cast<uint64_t*>(st.tsum.p), strm, done));
     }
     if (before_wait) HUFF_TRY(before_wait());
-    const uint64_t* hw = static_cast<const uint64_t*>(ctx->pin_total.p);
-    SpinWait sw;
-    for (;;) {
-        const uint64_t v = __atomic_load_n(hw, __ATOMIC_ACQUIRE);
-        if ((v >> 48) == done.tag) {
-            // (a fault in the kernels before the scan stops the stream before
-            // the scan publishes: the wait's liveness check reports it)
-            st.total = v & ((1ull << 48) - 1);
-            if (std::getenv("HUFF_FIX_STATS")) {  // diagnostics: how much the fix-up did (a synchronising copy)
-                unsigned int f[8];
-                HIP_TRY(hipMemcpyAsync(f, st.flag.p, sizeof f, hipMemcpyDeviceToHost, strm));
-                HIP_TRY(hipStreamSynchronize(strm));
-                static_assert(dev::kFixRounds == 4, "the line below prints four round flags");
-                std::fprintf(stderr,
-                             "huff fix-up: segments %llu, listed by the speculative pass %u, chain fixes %u, "
-                             "segment bits %llu, rounds %u %u %u %u\n",
-                             static_cast<unsigned long long>(nseg), f[dev::kFixRounds], f[dev::kFixRounds + 3],
-                             static_cast<unsigned long long>(S), f[0], f[1], f[2], f[3]);
-            }
-            return Status::ok();
-        }
-        if (sw.check_due()) {
-            const hipError_t q = hipStreamQuery(strm);
-            if (q == hipSuccess && (__atomic_load_n(hw, __ATOMIC_ACQUIRE) >> 48) != done.tag)
-                return Status::err(HUFF_E_HIP, "the index-free scan finished without publishing its total");
-            if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
-        }
+    HUFF_TRY(ctx->total.wait(strm, done.tag, &st.total, 1, "the index-free scan finished without publishing its total"));
+    if (std::getenv("HUFF_FIX_STATS")) {  // diagnostics: how much the fix-up did (a synchronising copy)
+        unsigned int f[8];
+        HIP_TRY(hipMemcpyAsync(f, st.flag.p, sizeof f, hipMemcpyDeviceToHost, strm));
+        HIP_TRY(hipStreamSynchronize(strm));
+        static_assert(dev::kFixRounds == 4, "the line below prints four round flags");
+        std::fprintf(stderr,
+                     "huff fix-up: segments %llu, listed by the speculative pass %u, chain fixes %u, "
+                     "segment bits %llu, rounds %u %u %u %u\n",
+                     static_cast<unsigned long long>(nseg), f[dev::kFixRounds], f[dev::kFixRounds + 3],
+                     static_cast<unsigned long long>(S), f[0], f[1], f[2], f[3]);
     }
+    return Status::ok();
 }
 
 Status indexless_mark(huff_ctx* ctx, IndexlessSync& st, DevBuf& sub_abs, uint32_t shift) {
@@ -1391,113 +1133,6 @@ Status indexless_mark(huff_ctx* ctx, IndexlessSync& st, DevBuf& sub_abs, uint32_
     HIP_TRY(dev::launch_indexless_mark(st.a, static_cast<const uint64_t*>(st.off.p),
                                        static_cast<uint64_t*>(sub_abs.p), shift, ctx->stream));
     return Status::ok();
-}
-
-// HUFF_SYNC_DECODE=1: the one-pass index-free decoder (syncdec.hip) where it
-// applies. Opt-in: measured slower than the pipeline (1 GiB
-// Zipf 1.52-1.70 vs 1.04 ms; its look-back waits and variable-length output
-// cost more than the second walk they save); the tests run both.
-static bool sync_decode_enabled() {
-    const char* e = std::getenv("HUFF_SYNC_DECODE");
-    return e && *e == '1';
-}
-
-// The one-pass index-free decoder (syncdec.hip) into the caller's buffer.
-// *done false: it does not apply, or it reported that its tail job list
-// overflowed (pathologically skewed streams): the pipeline decodes instead.
-static Status decode_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t valid_bits,
-                          const huff_tree* t, const DecTables* dt, uint8_t* d_user, size_t user_cap, bool* done,
-                          uint64_t* nsym) {
-    *done = false;
-    if (!sync_decode_enabled() || dt->maxdepth > dt->sbits || dt->sbits < 1 || dt->sbits > 12) return Status::ok();
-    uint32_t g = 0, lo_, hi_;
-    t->t.depth_range(&lo_, &hi_, &g);
-    if (g == 0) g = 1;
-    // segments holding ~0.72 kSyncCap letters at the tree's Kraft mean, at an
-    // odd dword stride (S = 32 mod 64: lanes start on different LDS banks),
-    // a multiple of the gcd of the code lengths (every start in phase)
-    const double target = 0.72 * dev::kSyncCap * dt->kraft_bits;
-    uint64_t kmax = std::max<uint64_t>(1, static_cast<uint64_t>(target) / g);
-    uint64_t S = g * kmax;
-    for (uint64_t k = kmax; k >= 1 && k + 64 >= kmax; --k)
-        if ((g * k) % 64 == 32) {
-            S = g * k;
-            break;
-        }
-    // lead-ins (HUFF_SYNC_LEAD / _LEAD0 for A/B): every lane's, and the
-    // longer one of a tile's first lane
-    auto env_u = [](const char* k, uint32_t d) {
-        const char* e = std::getenv(k);
-        return e && *e ? static_cast<uint32_t>(std::strtoul(e, nullptr, 10)) : d;
-    };
-    const uint32_t lead = std::max<uint32_t>(g, env_u("HUFF_SYNC_LEAD", 96) / g * g);
-    const uint32_t lead0 = std::max<uint32_t>(lead, env_u("HUFF_SYNC_LEAD0", 256) / g * g);
-    S = std::min<uint64_t>(std::max<uint64_t>(S, lead0), 1024 / g * g);
-    const uint64_t nseg = (valid_bits + S - 1) / S;
-    const uint64_t ntiles = (nseg + 255) / 256;
-    if (ntiles > 0x7FFFFFFFull) return Status::ok();
-    HUFF_TRY(ctx->sd_ws.ensure(32 + ntiles * 8));
-    const uint64_t job_cap = nseg / 8 + 1024;
-    HUFF_TRY(ctx->sd_jobs.ensure(job_cap * 24));
-    HUFF_TRY(ctx->pin_total.ensure(8));
-    if (!ctx->pin_total_dev) {
-        std::memset(ctx->pin_total.p, 0, 8);
-        HIP_TRY(hipHostGetDevicePointer(&ctx->pin_total_dev, ctx->pin_total.p, 0));
-    }
-    ctx->total_seq = (ctx->total_seq % 0xFFFF) + 1;
-    uint8_t* ws = static_cast<uint8_t*>(ctx->sd_ws.p);
-    dev::SyncDecArgs a{};
-    a.comp = d_comp;
-    a.comp_bytes = comp_bytes;
-    a.valid_bits = valid_bits;
-    a.seg_bits = S;
-    a.nseg = nseg;
-    a.lead_bits = lead;
-    a.lead0_bits = lead0;
-    a.stab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->soff);
-    a.stab_bits = dt->sbits;
-    a.out = d_user;
-    a.out_cap = user_cap;
-    a.ctrl = reinterpret_cast<unsigned int*>(ws);
-    a.total = reinterpret_cast<unsigned long long*>(ws + 16);
-    a.tile = reinterpret_cast<unsigned long long*>(ws + 32);
-    a.jobs = static_cast<uint64_t*>(ctx->sd_jobs.p);
-    a.job_cap = job_cap;
-    a.host_total = static_cast<unsigned long long*>(ctx->pin_total_dev);
-    a.tag = ctx->total_seq;
-#ifdef HUFF_STAMPS
-    a.stamps = stamp_region(0);
-#endif
-    HIP_TRY(hipMemsetAsync(ws, 0, 32 + ntiles * 8, ctx->stream));
-    HIP_TRY(dev::launch_sync_decode(a, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->lut_free, ctx->stream));
-    const uint64_t* hw = static_cast<const uint64_t*>(ctx->pin_total.p);
-    SpinWait sw;
-    for (;;) {
-        const uint64_t v = __atomic_load_n(hw, __ATOMIC_ACQUIRE);
-        if ((v >> 48) == a.tag) {
-            const uint64_t n = v & dev::kSyncBad;
-            if (std::getenv("HUFF_FIX_STATS")) {  // diagnostics: the tail's jobs (a synchronising copy)
-                unsigned int c[4];
-                HIP_TRY(hipMemcpyAsync(c, a.ctrl, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                std::fprintf(stderr, "huff sync decode: segments %llu of %llu bits, tail jobs %u, look-back waits %u, %s\n",
-                             static_cast<unsigned long long>(nseg), static_cast<unsigned long long>(S), c[dev::kSyncJobs],
-                             c[dev::kSyncMis],
-                             n == dev::kSyncBad ? "fell back to the pipeline" : "done");
-            }
-            if (n == dev::kSyncBad) return Status::ok();  // the pipeline instead
-            *nsym = n;
-            *done = true;
-            return Status::ok();
-        }
-        if (sw.check_due()) {
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q == hipSuccess && (__atomic_load_n(hw, __ATOMIC_ACQUIRE) >> 48) != a.tag)
-                return Status::err(HUFF_E_HIP, "the one-pass index-free decode finished without publishing its count");
-            if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
-        }
-    }
 }
 
 Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t valid_bits,
@@ -1584,11 +1219,6 @@ Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_
         return Status::ok();
     }
     const uint32_t check = decode_check_mode();
-    if (d_user && !d_end && !check) {  // one pass (syncdec.hip), when it applies
-        bool done = false;
-        HUFF_TRY(decode_sync(ctx, d_comp, comp_bytes, valid_bits, t, dt, d_user, user_cap, &done, nsym));
-        if (done) return out_ptr(*nsym);  // (a short buffer: nothing past it was written)
-    }
     IndexlessSync& st = ctx->indexless_ws();
     st.dt = dt;
     // with a caller's buffer, the marks go out before the host waits for the
@@ -1660,9 +1290,7 @@ Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_
         dev::DecodeArgs d{};
         d.comp = d_comp;
         d.comp_bytes = comp_bytes;
-        d.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
-        d.lut_bits = dt->bits;
-        d.lut_words = static_cast<uint32_t>(dt->lut.size());
+        fill_fixed_decode(d, ctx, dt, valid_bits, total);
         d.sub_abs64 = compact ? nullptr : static_cast<const uint64_t*>(sub_abs.p);
         d.mark32 = compact ? static_cast<const uint32_t*>(ctx->idx_mark32.p) : nullptr;
         d.task_seg = compact ? static_cast<const uint32_t*>(ctx->idx_task_seg.p) : nullptr;
@@ -1670,14 +1298,6 @@ Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_
         d.skip_packed = check ? 0u : 1u;
         d.end_bit = valid_bits;
         d.nchunks = static_cast<uint32_t>((total + dev::kChunk - 1) / dev::kChunk);
-        d.max_len = dt->maxdepth;
-        d.stab = reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(ctx->d_lut.p) + dt->soff);
-        d.stab_bits = dt->sbits;
-        d.cu_count = static_cast<uint32_t>(ctx->cu_count);
-        d.pad_stage = dev::fixed_decode_pad(valid_bits, total);
-        d.small_stage = small_stage_enabled() && dev::fixed_decode_small(valid_bits, total);
-        d.refill_cap = decode_refill_cap();
-        d.n = total;
         d.out = bounce ? static_cast<uint8_t*>(ctx->d_align.p) : out_at();
         d.check_mode = check;
         HUFF_TRY(run_checked_decode(ctx, d, [&] { return dev::launch_decode_fixed(d, strm); }));

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../device/kernels.hpp"
+#include "../host/dectables.hpp"
 #include "../host/huff_coding.hpp"
 
 namespace huff {
@@ -39,38 +40,6 @@ struct EncTables {
     // words per letter (deep.hip)
     std::vector<uint32_t> deep;
 };
-
-struct DecTables {
-    std::vector<uint32_t> lut;  // primary [1 << bits] then 8-bit secondaries
-    uint32_t bits = 0;
-    uint32_t maxdepth = 0;
-    bool all8 = false;          // every leaf at depth 8: decode is a byte map
-    // single-symbol u16 table (decode_wave.hip k_decode_fixed), packed two
-    // entries per word at word `soff`: [1 << sbits] entries, used | letter << 8,
-    // kSsSlow for windows whose first code is longer than sbits
-    uint32_t sbits = 0, soff = 0;
-    // multi-code walk table (indexless.hip's speculative pass): [1 << sbits]
-    // u16 entries at word `woff`: first length | kSsSlow | used << 8 | count << 12
-    uint32_t woff = 0;
-    // level-2 length table for the sync kernels (codes longer than sbits,
-    // <= 32 bits): `l2words` words at word `l2off` = nd u32 descriptors
-    // (byte offset of the prefix's entries in this block << 5 | its index
-    // bits E) then u8 code lengths; the slow entries of stab and the walk
-    // table carry their descriptor index in bits [0, 7) and [8, 16). 0: none
-    // l2E > 0: the uniform form instead, no descriptors: every slow window s
-    // has 2^l2E lengths at byte s << l2E (l2E = the deepest leaf below any
-    // slow window), indexed by the l2E bits after the first sbits; the slow
-    // entries carry s the same way
-    uint32_t l2off = 0, l2words = 0, l2E = 0;
-    // mean code length weighted 2^-len (the Kraft mean: the mean of the
-    // single-symbol table's lengths), the one-pass index-free decoder's guess
-    // of bits per letter when it sizes its segments (syncdec.hip)
-    double kraft_bits = 8.0;
-    // the uniform form, and more than 1/64 of the windows slow (a 64-lane
-    // step then nearly always has a slow lane)
-    bool l2dense = false;
-};
-
 
 // The run-time test knobs (listed with their values and users at their
 // definitions in runtime.cpp; each reads the environment per call).
@@ -97,8 +66,6 @@ struct PackStamps {
     std::chrono::steady_clock::time_point bits, launch, launched;
 };
 PackStamps& pack_stamps();
-
-Status build_dec_tables(const HuffTree& t, DecTables& out);
 
 }  // namespace huff
 
@@ -147,6 +114,21 @@ struct DevBuf {
     ~DevBuf() { release(); }
 };
 
+// Words that a kernel publishes straight to pinned host memory, each as
+// (tag << 48) | value in one 8-byte store, and that the host spins for (a
+// copy and a stream synchronisation in their place cost ~40 us).
+struct TaggedWords {
+    PinnedBuf pin;
+    void* dev = nullptr;  // the device's address of pin.p
+    uint64_t seq = 0;     // the last launch's tag
+    // what the publishing launch takes: the words (zeroed on first use) and
+    // the next tag, 1..65535: never the zeroed buffer's
+    huff::Status arm(size_t words, huff::dev::HistDone* done);
+    // out[i] = the value of word i once it carries `tag`, in order; `what`
+    // is the error if the stream ends without the words
+    huff::Status wait(hipStream_t s, uint64_t tag, uint64_t* out, size_t words, const char* what);
+};
+
 namespace huff {
 struct IndexlessSync;
 struct FileWs;
@@ -161,19 +143,20 @@ struct huff_ctx {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;  // table uploads beside the kernels
     hipEvent_t lut_free = nullptr;      // after the last kernel that read d_lut
-    PinnedBuf pin_w;     // weights readback: 256 tagged totals written by pass 1
-    void* pin_w_dev = nullptr;
-    uint64_t hist_seq = 0;
+    TaggedWords weights;  // weights readback: 256 totals written by pass 1
     // a pass 1 queued ahead by huff_enc_hist_launch, not yet waited for: its
-    // job and tag (one at a time, as pin_w is the context's)
+    // job and tag (one at a time, as `weights` is the context's)
     const huff_enc* hist_pending = nullptr;
     uint64_t hist_pending_tag = 0;
-    PinnedBuf pin_total;  // the index-free decode's symbol count, tagged, written by its scan
-    void* pin_total_dev = nullptr;
-    uint64_t total_seq = 0;
+    TaggedWords total;   // the index-free decode's symbol count, written by its scan
     PinnedBuf pin_lut;   // decode table upload
     DevBuf d_in, d_out;  // staging of the host-pointer API
     DevBuf d_lut;
+    // a u16 table of the uploaded decode tables, at word `off` of d_lut
+    // (DecTables::soff, woff)
+    const uint16_t* lut_u16(uint32_t off) const {
+        return reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(d_lut.p) + off);
+    }
     DevBuf d_align;      // aligned decode target for a misaligned output pointer
     DevBuf d_comp_align; // aligned copy of a misaligned index-free input stream
     DevBuf d_err;        // k_decode_fixed self-check record (check builds)
@@ -182,7 +165,6 @@ struct huff_ctx {
     std::shared_ptr<huff::IndexlessSync> idx_ws;
     DevBuf idx_sub_abs;
     DevBuf idx_mark32, idx_task_seg;  // the index-free decode's compact marks (k_mark_lite)
-    DevBuf sd_ws, sd_jobs;            // the one-pass index-free decoder's tile words / control, its tail jobs
     huff::IndexlessSync& indexless_ws();
     // the .hff file path's pinned pieces and device buffers (filepath.cpp),
     // kept across calls: pinning ~0.5 GB per call costs more than the copies
@@ -248,6 +230,9 @@ struct huff_enc {
     // until a consumer needs it: decode through a bit decoder, or download
     bool index_pending = false;
     huff::Status ensure_index();
+    // the end of every pack: the stream's tree, base and bits, and the state
+    // of its restart index
+    void set_packed(const huff_tree* t, uint64_t base, uint64_t bits, bool pending, bool compact);
 
     huff::Status init(huff_ctx* c, const uint8_t* d, uint64_t nbytes);
     huff::Status hist();
@@ -255,7 +240,6 @@ struct huff_enc {
     // (huff_enc_hist_launch)
     huff::Status hist_launch();
     huff::Status launch_publish(uint64_t* tag);
-    huff::Status wait_weights(uint64_t tag);
     // pass 1 when the counts are already known (the file path's second pass):
     // the per-chunk rows only, no host wait
     huff::Status hist_known(const uint64_t counts[256]);

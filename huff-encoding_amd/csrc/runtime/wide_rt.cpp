@@ -10,6 +10,14 @@ std::atomic<uint64_t> g_wtree_ids{1};
 constexpr size_t kTableLdsMax = 64 * 1024;  // stage the code hash table in LDS up to this
 }  // namespace
 
+// host/wide.hpp builds the tables the kernels read, to its own copies of
+// their constants
+static_assert(huff::kWideLutPtr == huff::dev::kLutPtr, "host/wide.hpp mirrors dev::kLutPtr");
+static_assert(huff::kWideLutMaxBits == huff::dev::kLutMaxBits, "host/wide.hpp mirrors dev::kLutMaxBits");
+static_assert(huff::kWideMaxDecodeLen == huff::dev::kLongMaxLen, "host/wide.hpp mirrors dev::kLongMaxLen");
+static_assert(huff::kWideMaxEncodeLen == huff::dev::kLongMaxLen - 1, "host/wide.hpp mirrors dev::kLongMaxLen - 1");
+static_assert(huff::kWideShortMax == huff::dev::kShortMaxLen, "host/wide.hpp mirrors dev::kShortMaxLen");
+
 #define HIP_TRY(expr) HIP_TRY_RT(expr)
 
 using huff::Status;

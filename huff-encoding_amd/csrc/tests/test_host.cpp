@@ -11,6 +11,7 @@
 #include <random>
 #include <vector>
 
+#include "host/dectables.hpp"
 #include "host/huff_coding.hpp"
 #include "host/rust_heap.hpp"
 
@@ -219,7 +220,321 @@ static void tree_fast_path_matches_heap() {
     CHECK(bad == 0);
 }
 
+// ---------------------------------------------------------------------------
+// decode tables (host/dectables.cpp): every entry of every table against a
+// bit-by-bit walk of the tree written here
+// ---------------------------------------------------------------------------
+
+// the tree walked over the `m` bits of `v`, MSB first, from `from` (-1: the
+// root): the first leaf met (len bits used), else the node the bits end on
+struct Walked {
+    bool leaf;
+    uint32_t len;
+    uint8_t letter;
+    int32_t node;
+};
+static Walked walk_bits(const HuffTree& t, uint64_t v, uint32_t m, int32_t from = -1) {
+    const auto& nd = t.nodes();
+    if (t.root_is_leaf()) return {true, 1, nd[t.root()].letter, t.root()};  // every bit is the root letter
+    int32_t x = from < 0 ? t.root() : from;
+    for (uint32_t p = 0; p < m; ++p) {
+        x = ((v >> (m - 1 - p)) & 1u) ? nd[x].right : nd[x].left;
+        if (nd[x].is_leaf) return {true, p + 1, nd[x].letter, x};
+    }
+    return {false, m, 0, x};
+}
+
+static uint32_t deepest_below(const HuffTree& t, int32_t x) {
+    const auto& n = t.nodes()[x];
+    return n.is_leaf ? 0u : 1u + std::max(deepest_below(t, n.left), deepest_below(t, n.right));
+}
+
+static uint16_t u16_at(const DecTables& d, uint32_t word_off, uint32_t i) {
+    uint16_t e;
+    std::memcpy(&e, reinterpret_cast<const uint8_t*>(d.lut.data() + word_off) + 2 * i, 2);
+    return e;
+}
+
+// the lut table at `base` (tb index bits) below node x at depth d0, and the
+// secondaries it links; returns how many tables, *chain = the longest chain
+static uint32_t check_lut(const HuffTree& t, const DecTables& d, uint32_t base, int32_t x, uint32_t d0, uint32_t tb,
+                          uint32_t depth, uint32_t* chain) {
+    uint32_t tables = 1;
+    *chain = std::max(*chain, depth);
+    int bad = 0;
+    for (uint32_t i = 0; i < (1u << tb); ++i) {
+        const Walked w = walk_bits(t, i, tb, x);
+        const uint32_t e = d.lut[base + i];
+        if (w.leaf) {
+            bad += e != (((d0 + w.len) << 8) | w.letter);
+            continue;
+        }
+        const uint32_t sub = e & ~kLutPtr;
+        if (!(e & kLutPtr) || sub < (1u << d.bits) || sub + 256 > d.soff || (sub - (1u << d.bits)) % 256) {
+            ++bad;
+            continue;
+        }
+        tables += check_lut(t, d, sub, w.node, d0 + tb, 8, depth + 1, chain);
+    }
+    CHECK(bad == 0);
+    return tables;
+}
+
+struct TableFacts {
+    uint32_t slow = 0;        // slow windows of the single table
+    uint32_t secondaries = 0; // 8-bit tables behind the primary
+    uint32_t chain = 0;       // the longest chain of secondaries
+};
+
+static TableFacts check_tables(const HuffTree& t, const DecTables& d);
+
+// (names the tree whose tables failed)
+static TableFacts check_dec_tables(const char* tree, const HuffTree& t, const DecTables& d) {
+    const int before = g_fail;
+    const TableFacts f = check_tables(t, d);
+    if (g_fail != before) std::printf("  ^ decode tables of the tree: %s\n", tree);
+    return f;
+}
+
+static TableFacts check_tables(const HuffTree& t, const DecTables& d) {
+    TableFacts f;
+    uint32_t lo = 0, hi = 0;
+    t.depth_range(&lo, &hi);
+    CHECK(d.maxdepth == hi);
+    CHECK(d.bits == std::max(1u, std::min(hi, kLutMaxBits - 1)));
+    CHECK(d.sbits == std::min(hi, kSsMaxBits));
+    const uint32_t K = d.sbits, n = 1u << K;
+    // primary and secondary lut
+    if (t.root_is_leaf()) {
+        const uint32_t e = (1u << 8) | t.nodes()[t.root()].letter;
+        CHECK(d.bits == 1 && d.soff == 2 && d.lut[0] == e && d.lut[1] == e);
+    } else {
+        f.secondaries = check_lut(t, d, 0, t.root(), 0, d.bits, 0, &f.chain) - 1;
+        CHECK(d.soff == (1u << d.bits) + 256 * f.secondaries);
+    }
+    CHECK(d.woff == d.soff + (n + 1) / 2);
+    // single and walk tables; the slow windows in ascending order
+    std::vector<uint32_t> slow;
+    int bad_s = 0, bad_w = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        const Walked first = walk_bits(t, v, K);
+        const uint16_t s = u16_at(d, d.soff, v), w = u16_at(d, d.woff, v);
+        if (first.leaf) {
+            bad_s += s != (first.len | (uint32_t(first.letter) << 8));
+        } else {
+            bad_s += !(s & kSsSlow) || (!d.l2words && s != kSsSlow);
+            slow.push_back(v);
+        }
+        uint32_t used = 0, count = 0;
+        for (;;) {  // greedily, every complete code of the window
+            const Walked c = walk_bits(t, v & ((1u << (K - used)) - 1), K - used);
+            if (!c.leaf || c.len > K - used) break;
+            used += c.len;
+            ++count;
+        }
+        if (count) bad_w += w != (first.len | (used << 8) | (count << 12));
+        else bad_w += !(w & kSsSlow) || (!d.l2words && w != kSsSlow);
+        bad_w += (count == 0) != !first.leaf;
+    }
+    CHECK(bad_s == 0);
+    CHECK(bad_w == 0);
+    f.slow = static_cast<uint32_t>(slow.size());
+    if (!d.l2words) {
+        CHECK(d.l2E == 0 && !d.l2dense);
+        CHECK(d.lut.size() == d.woff + (n + 1) / 2);
+        return f;
+    }
+    // level 2: the slow windows' indices, then the lengths below each
+    CHECK(d.l2off == d.woff + (n + 1) / 2 && d.lut.size() == d.l2off + d.l2words);
+    CHECK(!slow.empty() && hi > K && hi <= 32);
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(d.lut.data() + d.l2off);
+    size_t bytes = d.l2E ? slow.size() << d.l2E : slow.size() * 4;
+    int bad_i = 0, bad_d = 0, bad_l = 0;
+    for (uint32_t s = 0; s < slow.size(); ++s) {
+        const uint16_t want = static_cast<uint16_t>(kSsSlow | (s & 0x7Fu) | ((s >> 7) << 8));
+        bad_i += u16_at(d, d.soff, slow[s]) != want || u16_at(d, d.woff, slow[s]) != want;
+        uint32_t E = d.l2E;
+        size_t at = size_t(s) << d.l2E;
+        if (!d.l2E) {  // the descriptor: byte offset << 5 | E
+            uint32_t desc;
+            std::memcpy(&desc, b + 4 * s, 4);
+            E = deepest_below(t, walk_bits(t, slow[s], K).node);
+            at = bytes;
+            bad_d += desc != ((bytes << 5) | E);
+            bytes += size_t(1) << E;
+            if (bytes > size_t(d.l2words) * 4) break;
+        }
+        for (uint32_t j = 0; j < (1u << E); ++j) {
+            const Walked c = walk_bits(t, (uint64_t(slow[s]) << E) | j, K + E);
+            bad_l += b[at + j] != (c.leaf ? c.len : K + E);
+        }
+    }
+    CHECK(bad_i == 0);
+    CHECK(bad_d == 0);
+    CHECK(bad_l == 0);
+    CHECK(d.l2words == (bytes + 15) / 16 * 4);
+    return f;
+}
+
+static HuffTree tree_of(const std::vector<uint64_t>& w) {
+    std::vector<uint8_t> l(w.size());
+    for (size_t i = 0; i < w.size(); ++i) l[i] = static_cast<uint8_t>(i * 37 + 11);  // distinct, not the index
+    HuffTree t;
+    CHECK(!HuffTree::from_leaves(l.data(), w.data(), w.size(), t));
+    return t;
+}
+
+// a chain: every weight above the sum of those before it, depth n - 1
+static std::vector<uint64_t> chain_weights(size_t n) {
+    std::vector<uint64_t> w{1, 1};
+    while (w.size() < n) w.push_back(uint64_t(3) << (w.size() - 2));
+    return w;
+}
+
+// ones (depth 13) and twos (depth 12) filling a balanced subtree of 128 nodes
+// at depth 12 under a five-leaf chain: 65 of the 4,096 windows are slow, each
+// with two leaves below; `deep` hangs a chain of 9 leaves in place of a one
+static std::vector<uint64_t> bushy_weights(bool deep) {
+    std::vector<uint64_t> w;
+    if (deep)
+        for (uint64_t c : chain_weights(9)) w.push_back(c);  // sums to 383: pairs with the odd 300
+    for (int i = deep ? 1 : 0; i < 130; ++i) w.push_back(300);
+    for (int i = 0; i < 63; ++i) w.push_back(600);
+    for (uint64_t c = 80000; c <= 1280000; c *= 2) w.push_back(c);
+    return w;
+}
+
+static DecTables tables_of(const HuffTree& t, bool sparse = false) {
+    DecTables d;
+    CHECK(!build_dec_tables(t, sparse, d));
+    return d;
+}
+
+static void dec_tables_one_letter() {
+    const HuffTree t = tree_of({78});
+    const DecTables d = tables_of(t);
+    CHECK(t.root_is_leaf() && d.bits == 1 && d.sbits == 1 && d.maxdepth == 1 && !d.all8);
+    const TableFacts f = check_dec_tables("one letter", t, d);
+    CHECK(f.slow == 0 && d.l2words == 0);
+}
+
+static void dec_tables_two_letters() {
+    const HuffTree t = tree_of({3, 5});
+    const DecTables d = tables_of(t);
+    CHECK(!t.root_is_leaf() && d.bits == 1 && d.sbits == 1 && d.maxdepth == 1);
+    const TableFacts f = check_dec_tables("two letters", t, d);
+    CHECK(f.slow == 0 && f.secondaries == 0);
+}
+
+static void dec_tables_all8() {
+    ByteWeights w;
+    for (auto& x : w.weights) x = 7;
+    w.len = 256;
+    HuffTree t;
+    CHECK(!HuffTree::from_weights(w, t));
+    const DecTables d = tables_of(t);
+    CHECK(d.all8 && d.bits == 8 && d.sbits == 8);
+    const TableFacts f = check_dec_tables("256 equal weights", t, d);
+    CHECK(f.slow == 0 && f.secondaries == 0);
+}
+
+static void dec_tables_depth_11() {
+    const HuffTree t = tree_of(chain_weights(12));
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 11 && d.bits == 11 && d.sbits == 11 && !d.all8);
+    const TableFacts f = check_dec_tables("depth 11", t, d);
+    CHECK(f.secondaries == 0 && f.slow == 0 && d.l2words == 0);
+}
+
+static void dec_tables_depth_12() {
+    const HuffTree t = tree_of(chain_weights(13));
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 12 && d.bits == 11 && d.sbits == 12);
+    const TableFacts f = check_dec_tables("depth 12", t, d);
+    CHECK(f.secondaries > 0 && f.slow == 0 && d.l2words == 0);
+}
+
+static void dec_tables_l2_uniform_sparse() {
+    // a chain with a pair of leaves hanging off every level: the running sum
+    // S and the last pair P merge before the next pair (a, b) does, as
+    // max(S, P) < a <= b < S + P. Depth 16; the chain's node and the pair's
+    // at depth 12 are the two slow windows
+    std::vector<uint64_t> w{4, 6, 8, 9};
+    for (uint64_t S = 10, P = 17; w.size() < 32;) {
+        const uint64_t a = std::max(S, P) + 1, b = S + P - 1;
+        w.push_back(a);
+        w.push_back(b);
+        S += P;
+        P = a + b;
+    }
+    const HuffTree t = tree_of(w);
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 16 && d.l2words > 0 && d.l2E == 4 && !d.l2dense);
+    const TableFacts f = check_dec_tables("level 2 uniform, few slow windows", t, d);
+    CHECK(f.slow == 2);
+}
+
+static void dec_tables_l2_uniform_dense() {
+    const HuffTree t = tree_of(bushy_weights(false));
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 13 && d.l2words > 0 && d.l2E == 1 && d.l2dense);
+    const TableFacts f = check_dec_tables("level 2 uniform, dense", t, d);
+    CHECK(f.slow > 64);
+    // the sparse flag: the same words, the branching walk
+    const DecTables s = tables_of(t, true);
+    CHECK(!s.l2dense && s.lut == d.lut && s.l2E == d.l2E && s.l2off == d.l2off && s.l2words == d.l2words);
+    CHECK(s.bits == d.bits && s.sbits == d.sbits && s.soff == d.soff && s.woff == d.woff && s.maxdepth == d.maxdepth);
+    check_dec_tables("level 2 uniform, dense, sparse flag", t, s);
+}
+
+static void dec_tables_l2_descriptors() {
+    const HuffTree t = tree_of(bushy_weights(true));
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 21 && d.l2words > 0 && d.l2E == 0 && !d.l2dense);
+    const TableFacts f = check_dec_tables("level 2 descriptors", t, d);
+    // the uniform form would not fit, the descriptors do
+    CHECK((size_t(f.slow) << (d.maxdepth - d.sbits)) > 24 * 1024 && size_t(d.l2words) * 4 <= 24 * 1024);
+}
+
+static void dec_tables_l2_fits_neither() {
+    const HuffTree t = tree_of(chain_weights(28));  // one slow window, 2^15 lengths below it
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 27 && d.maxdepth <= 32 && d.l2words == 0);
+    // (without a level 2, check_tables asks that the slow entries are plain kSsSlow)
+    const TableFacts f = check_dec_tables("level 2 fits neither form", t, d);
+    CHECK(f.slow == 1 && f.secondaries == 2);
+}
+
+static void dec_tables_depth_33() {
+    const HuffTree t = tree_of(chain_weights(34));
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth == 33 && d.l2words == 0);
+    const TableFacts f = check_dec_tables("depth 33", t, d);
+    CHECK(f.slow == 1 && f.chain == 3);
+}
+
+static void dec_tables_fibonacci() {
+    std::vector<uint64_t> w{1, 1};
+    while (w.size() < 60) w.push_back(w[w.size() - 1] + w[w.size() - 2]);
+    const HuffTree t = tree_of(w);
+    const DecTables d = tables_of(t);
+    CHECK(d.maxdepth > kLongMaxLen && d.l2words == 0);
+    const TableFacts f = check_dec_tables("Fibonacci, depth 59", t, d);
+    CHECK(f.chain == (d.maxdepth - d.bits + 7) / 8 && f.chain >= 6);
+}
+
 int main() {
+    dec_tables_one_letter();
+    dec_tables_two_letters();
+    dec_tables_all8();
+    dec_tables_depth_11();
+    dec_tables_depth_12();
+    dec_tables_l2_uniform_sparse();
+    dec_tables_l2_uniform_dense();
+    dec_tables_l2_descriptors();
+    dec_tables_l2_fits_neither();
+    dec_tables_depth_33();
+    dec_tables_fibonacci();
     shard_plan_matches_single_stream();
     tree_normal_init();
     tree_single_branch();

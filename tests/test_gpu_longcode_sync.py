@@ -153,9 +153,7 @@ def check_stream(H, O, ctx, L, data, misalign=0):
 
 
 def pipeline(monkeypatch):
-    """the pipeline's kernels and their diagnostics line (the one-pass decoder
-    does not apply past 12 bits anyway)"""
-    monkeypatch.setenv("HUFF_SYNC_DECODE", "0")
+    """the pipeline's kernels and their diagnostics line"""
     monkeypatch.setenv("HUFF_FIX_STATS", "1")
 
 

@@ -396,7 +396,7 @@ def test_index_free_capacity_below_count(W, O, ctx):
     torch.cuda.synchronize()
     L = _lib.load()
     for cap in (n - 1, n // 3, 65):
-        out.fill_(0x5A5A)  # (the one-pass decoder writes the letters that fit)
+        out.fill_(0x5A5A)
         torch.cuda.synchronize()
         got = C.c_size_t()
         rc = L.huff_dev_wdecompress(ctx.h, t.h, C.c_void_p(dc.data_ptr()), comp.size, pad,
