@@ -15,6 +15,7 @@
 #include "runtime/runtime.hpp"
 
 #include "capi_util.hpp"
+#include "host/batch_container.hpp"
 
 namespace huff::capi {
 
@@ -669,6 +670,197 @@ int huff_batch_decode(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_co
         a.status = d_status;
         HUFF_TRY(ctx->timed(d_sub ? "batch_decode" : "batch_decode_noindex",
                             [&] { return huff::dev::launch_batch_decode(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+namespace {
+
+// one u64 of device memory, read on the context's stream
+huff::Status read_total(huff_ctx* ctx, const uint64_t* d, uint64_t& v) {
+    HIP_TRY_RT(hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, ctx->stream));
+    return ctx->sync();
+}
+
+}  // namespace
+
+int huff_batch_blob_offsets(huff_ctx* ctx, const uint32_t* d_tree_nbits, const uint64_t* d_comp_offsets,
+                            const uint32_t* d_status, uint32_t nstreams, uint64_t* d_blob_offsets) {
+    if (!ctx || !d_blob_offsets || (nstreams && (!d_tree_nbits || !d_comp_offsets || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        huff::dev::BatchBlobArgs a{};
+        a.tree_nbits = d_tree_nbits;
+        a.comp_off = d_comp_offsets;
+        a.status = d_status;
+        a.nstreams = nstreams;
+        a.blob_off = d_blob_offsets;
+        HUFF_TRY(ctx->timed("batch_blob_offsets", [&] { return huff::dev::launch_batch_blob_offsets(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+int huff_batch_to_bytes(huff_ctx* ctx, const uint8_t* d_tree_bits, size_t tree_stride, const uint32_t* d_tree_nbits,
+                        const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                        const uint32_t* d_status, uint32_t nstreams, const uint64_t* d_blob_offsets, uint8_t* d_out,
+                        size_t out_cap) {
+    if (!ctx || !d_blob_offsets ||
+        (nstreams && (!d_tree_bits || !d_tree_nbits || !d_comp_offsets || !d_bits || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (tree_stride > 0xFFFFFFFFu) return fail(HUFF_E_INVALID_ARG, "tree_stride out of range");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        uint64_t total = 0;  // before anything is launched
+        HUFF_TRY(read_total(ctx, d_blob_offsets + nstreams, total));
+        if (total > out_cap) return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "batch blob capacity too small");
+        if (total && (!d_out || !d_comp)) return huff::Status::err(HUFF_E_INVALID_ARG, "null argument");
+        huff::dev::BatchBlobArgs a{};
+        a.tree_bits = d_tree_bits;
+        a.tree_stride = static_cast<uint32_t>(tree_stride);
+        a.tree_nbits = d_tree_nbits;
+        a.comp = d_comp;
+        a.comp_off = d_comp_offsets;
+        a.bits = d_bits;
+        a.status = d_status;
+        a.nstreams = nstreams;
+        a.blob_off = const_cast<uint64_t*>(d_blob_offsets);  // read only by to_bytes
+        a.out = d_out;
+        a.out_cap = out_cap;
+        HUFF_TRY(ctx->timed("batch_to_bytes", [&] { return huff::dev::launch_batch_to_bytes(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+int huff_batch_parse(huff_ctx* ctx, const uint8_t* d_blobs, const uint64_t* d_blob_offsets, uint32_t nstreams,
+                     uint8_t* d_tree_bits, size_t tree_stride, uint32_t* d_tree_nbits, uint64_t* d_codes,
+                     uint32_t* d_max_len, uint64_t* d_payload_begin, uint64_t* d_bits, uint64_t* d_comp_offsets,
+                     uint32_t* d_status) {
+    if (!ctx || !d_comp_offsets ||
+        (nstreams && (!d_blob_offsets || !d_tree_bits || !d_tree_nbits || !d_codes || !d_max_len ||
+                      !d_payload_begin || !d_bits || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (tree_stride < HUFF_TREE_BITS_MAX_BYTES || tree_stride > 0xFFFFFFFFu)
+        return fail(HUFF_E_INVALID_ARG, "tree_stride < HUFF_TREE_BITS_MAX_BYTES");
+    static_assert(static_cast<int>(huff::dev::kBatchFromBytes) == static_cast<int>(HUFF_E_FROM_BYTES) &&
+                      static_cast<int>(huff::dev::kBatchDeep) == static_cast<int>(HUFF_E_CODE_TOO_LONG) &&
+                      static_cast<int>(huff::dev::kBatchEmptyComp) == static_cast<int>(HUFF_E_EMPTY_COMP) &&
+                      static_cast<int>(huff::dev::kBatchPadding) == static_cast<int>(HUFF_E_PADDING) &&
+                      static_cast<int>(huff::dev::kBatchTreeLen) == static_cast<int>(HUFF_E_TREE_LEN),
+                  "the kernel writes the C ABI's status codes");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        if (nstreams && !d_blobs) {  // only empty slices can come without bytes
+            uint64_t total = 0;
+            HUFF_TRY(read_total(ctx, d_blob_offsets + nstreams, total));
+            if (total) return huff::Status::err(HUFF_E_INVALID_ARG, "null argument");
+        }
+        huff::dev::BatchParseArgs a{};
+        a.blobs = d_blobs;
+        a.blob_off = d_blob_offsets;
+        a.nstreams = nstreams;
+        a.tree_bits = d_tree_bits;
+        a.tree_stride = static_cast<uint32_t>(tree_stride);
+        a.tree_nbits = d_tree_nbits;
+        a.codes = d_codes;
+        a.max_len = d_max_len;
+        a.payload_begin = d_payload_begin;
+        a.bits = d_bits;
+        a.comp_off = d_comp_offsets;
+        a.status = d_status;
+        HUFF_TRY(ctx->timed("batch_parse", [&] { return huff::dev::launch_batch_parse(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+int huff_batch_unwrap(huff_ctx* ctx, const uint8_t* d_blobs, const uint64_t* d_payload_begin,
+                      const uint64_t* d_comp_offsets, const uint32_t* d_status, uint32_t nstreams, uint8_t* d_comp,
+                      size_t comp_cap) {
+    if (!ctx || !d_comp_offsets || (nstreams && (!d_payload_begin || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        uint64_t total = 0;
+        HUFF_TRY(read_total(ctx, d_comp_offsets + nstreams, total));
+        if (total > comp_cap) return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "batch payload capacity too small");
+        if (total && (!d_blobs || !d_comp)) return huff::Status::err(HUFF_E_INVALID_ARG, "null argument");
+        huff::dev::BatchUnwrapArgs a{};
+        a.blobs = d_blobs;
+        a.payload_begin = d_payload_begin;
+        a.comp_off = d_comp_offsets;
+        a.status = d_status;
+        a.nstreams = nstreams;
+        a.comp = d_comp;
+        a.comp_cap = comp_cap;
+        HUFF_TRY(ctx->timed("batch_unwrap", [&] { return huff::dev::launch_batch_unwrap(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+size_t huff_batch_seg_entries(size_t total_comp_bytes, uint32_t nstreams) {
+#ifndef HUFF_BATCH_SEG_BITS_AB
+    static_assert(HUFF_BATCH_SEG_BITS == huff::kBatchSegBits, "the header states the kernels' segment");
+#endif
+    return static_cast<size_t>(huff::batch_seg_entries(total_comp_bytes, nstreams));
+}
+
+int huff_batch_count(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                     const uint64_t* d_codes, const uint32_t* d_status_in, uint32_t nstreams, uint64_t* d_seg,
+                     size_t seg_cap, uint64_t* d_counts, uint32_t* d_status) {
+    if (!ctx || !d_comp_offsets || (nstreams && (!d_bits || !d_codes || !d_status_in || !d_counts || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        uint64_t total = 0;
+        HUFF_TRY(read_total(ctx, d_comp_offsets + nstreams, total));
+        if (huff::batch_seg_entries(total, nstreams) > seg_cap)
+            return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "batch segment scratch too small");
+        if (total && (!d_comp || !d_seg)) return huff::Status::err(HUFF_E_INVALID_ARG, "null argument");
+        huff::dev::BatchCountArgs a{};
+        a.comp = d_comp;
+        a.comp_off = d_comp_offsets;
+        a.bits = d_bits;
+        a.codes = d_codes;
+        a.status_in = d_status_in;
+        a.nstreams = nstreams;
+        a.seg = d_seg;
+        a.seg_cap = seg_cap;
+        a.counts = d_counts;
+        a.status = d_status;
+        HUFF_TRY(ctx->timed("batch_count", [&] { return huff::dev::launch_batch_count(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
+int huff_batch_index(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                     const uint64_t* d_codes, const uint64_t* d_seg, const uint64_t* d_offsets,
+                     const uint64_t* d_index_offsets, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub,
+                     size_t sub_cap) {
+    if (!ctx || !d_comp_offsets || !d_index_offsets ||
+        (nstreams && (!d_bits || !d_codes || !d_offsets || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        uint64_t total = 0, nsub = 0;
+        HUFF_TRY(read_total(ctx, d_comp_offsets + nstreams, total));
+        HUFF_TRY(read_total(ctx, d_index_offsets + nstreams, nsub));
+        if (nsub > sub_cap) return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "batch index capacity too small");
+        if ((total && (!d_comp || !d_seg)) || (nsub && !d_sub))
+            return huff::Status::err(HUFF_E_INVALID_ARG, "null argument");
+        huff::dev::BatchIndexArgs a{};
+        a.comp = d_comp;
+        a.comp_off = d_comp_offsets;
+        a.bits = d_bits;
+        a.codes = d_codes;
+        a.seg = d_seg;
+        a.seg_cap = huff::batch_seg_entries(total, nstreams);  // what huff_batch_count was given at least
+        a.off = d_offsets;
+        a.idx_off = d_index_offsets;
+        a.status = d_status;
+        a.nstreams = nstreams;
+        a.sub = d_sub;
+        a.sub_cap = sub_cap;
+        HUFF_TRY(ctx->timed("batch_index", [&] { return huff::dev::launch_batch_index(a, ctx->stream); }));
         return ctx->sync();
     });
 }

@@ -26,6 +26,7 @@
 //                  [kIdx j, kIdx j + kIdx) from sub[j] and must end at
 //                  sub[j + 1] (the last lane: at bits[s]). Without an index
 //                  one lane walks the stream.
+#include "batch_lut.hpp"
 #include "pack_emit.hpp"
 
 namespace huff::dev {
@@ -41,9 +42,6 @@ namespace {
 #endif
 #ifndef HUFF_BATCH_TILE
 #define HUFF_BATCH_TILE 16
-#endif
-#ifndef HUFF_BATCH_LUT_BITS
-#define HUFF_BATCH_LUT_BITS 12
 #endif
 #ifndef HUFF_BATCH_STAGE
 #define HUFF_BATCH_STAGE 1
@@ -266,49 +264,9 @@ __global__ __launch_bounds__(kBThreads) void k_batch_pack(BatchPackArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-constexpr uint32_t kBdLutBits = HUFF_BATCH_LUT_BITS;
-constexpr uint32_t kBdSlow = 0xFFu;    // len field of a table entry: the code is longer than the index
 // LDS for a round's compressed bytes: kBThreads lanes x kIdx letters of 9 bits on
 // average (incompressible bytes fit with their slack); a longer round reads global memory
 constexpr uint32_t kBdStageBytes = kBThreads * kIdx * 9 / 8;
-constexpr uint32_t kBdCoop = 32;       // spans above this many entries are filled by the whole workgroup
-
-// the stream's compressed bytes as big-endian words; bytes past the end read 0
-struct BatchSrc {
-    const uint8_t* p;
-    uint32_t nbytes;
-    __device__ __forceinline__ uint32_t word(uint32_t i) const {
-        const uint64_t byte = static_cast<uint64_t>(i) * 4;
-        if (byte + 4 <= nbytes) {
-            uint32_t v;
-            __builtin_memcpy(&v, p + byte, 4);  // any alignment
-            return __builtin_bswap32(v);
-        }
-        uint32_t v = 0;
-        for (int k = 0; k < 4; ++k) {
-            v <<= 8;
-            if (byte + k < nbytes) v |= p[byte + k];
-        }
-        return v;
-    }
-};
-
-// a round's compressed bytes staged in LDS: bytes [b0, b0 + span) of the
-// stream (b0 a multiple of 4); everything outside reads 0
-struct BatchSrcLds {
-    const uint8_t* lds;  // 16-B aligned
-    uint32_t b0, span;
-    __device__ __forceinline__ uint32_t word(uint32_t i) const {
-        const uint32_t off = i * 4 - b0;  // wraps to a large value below b0
-        if (span >= 4 && off <= span - 4) return __builtin_bswap32(*reinterpret_cast<const uint32_t*>(lds + off));
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            v <<= 8;
-            if (off + k < span) v |= lds[off + k];
-        }
-        return v;
-    }
-};
 
 // cnt symbols from bit `start`, which must end exactly at bit `end`; the
 // letters go to out[0, cnt) in 16-B pieces. False: a window without a code, or
@@ -335,20 +293,7 @@ __device__ __forceinline__ bool batch_decode_run(const Src& src, uint32_t start,
             const uint32_t e = lut[buf >> (64 - kBdLutBits)];
             uint32_t len = e & 0xFFu, letter = e >> 8;
             if (len == kBdSlow) {  // a code longer than the table's index: search the long codes, left-aligned
-                const uint32_t sh = pos & 31, w0 = pos >> 5;
-                uint64_t win = (static_cast<uint64_t>(src.word(w0)) << 32) | src.word(w0 + 1);
-                if (sh) win = (win << sh) | (src.word(w0 + 2) >> (32 - sh));
-                len = 0;
-                for (uint32_t i = 0; i < nlong; ++i) {
-                    const uint32_t l = longl[i];
-                    const uint64_t c = tab[l];
-                    const uint32_t cl = static_cast<uint32_t>(c & 0xFF);
-                    if ((win >> (64 - cl)) == (c >> 8)) {
-                        len = cl;
-                        letter = l;
-                        break;
-                    }
-                }
+                len = batch_long_code(src, pos, tab, longl, nlong, letter);
             }
             if (len == 0 || len > end - pos) return false;
             pos += len;
@@ -417,36 +362,8 @@ __global__ __launch_bounds__(TH) void k_batch_decode(BatchDecodeArgs a) {
         if (t == 0) a.status[s] = wrong ? kBatchCorrupt : kBatchOk;
         return;
     }
-    if (t == 0) nlong = ncoop = bad = 0;
-    for (uint32_t i = t; i < (1u << kBdLutBits) / 8; i += TH) reinterpret_cast<uint4*>(lut)[i] = make_uint4(0, 0, 0, 0);
-    static_assert(kBdLutBits >= 8 && kBdLutBits <= kSsMaxBits, "u16 entries, whole 16-B clears");
-    for (uint32_t l = t; l < 256; l += TH) tab[l] = a.codes[static_cast<uint64_t>(s) * 256 + l];
-    __syncthreads();
-    // letter l's span of the table: short spans by one thread, long ones by
-    // everyone; a longer code marks the entry of its first kBdLutBits bits
-    for (uint32_t l = t; l < 256; l += TH) {
-        const uint64_t c = tab[l];
-        const uint32_t len = static_cast<uint32_t>(c & 0xFF);
-        if (len > kBdLutBits) {
-            lut[static_cast<uint32_t>((c >> 8) >> (len - kBdLutBits))] = static_cast<uint16_t>(kBdSlow);
-            longl[atomicAdd(&nlong, 1u)] = static_cast<uint8_t>(l);
-        } else if (len) {
-            const uint32_t first = static_cast<uint32_t>(c >> 8) << (kBdLutBits - len), span = 1u << (kBdLutBits - len);
-            if (span > kBdCoop)
-                coopl[atomicAdd(&ncoop, 1u)] = static_cast<uint8_t>(l);
-            else
-                for (uint32_t i = 0; i < span; ++i) lut[first + i] = static_cast<uint16_t>((l << 8) | len);
-        }
-    }
-    __syncthreads();
-    for (uint32_t b = 0, nc = ncoop; b < nc; ++b) {
-        const uint32_t l = coopl[b];
-        const uint64_t cc = tab[l];
-        const uint32_t ll = static_cast<uint32_t>(cc & 0xFF);
-        const uint32_t first = static_cast<uint32_t>(cc >> 8) << (kBdLutBits - ll), sp = 1u << (kBdLutBits - ll);
-        for (uint32_t i = t; i < sp; i += TH) lut[first + i] = static_cast<uint16_t>((l << 8) | ll);
-    }
-    __syncthreads();
+    if (t == 0) bad = 0;
+    batch_build_lut<TH>(a.codes + static_cast<uint64_t>(s) * 256, lut, tab, longl, coopl, &nlong, &ncoop);
 
     const BatchSrc src{a.comp + c0, static_cast<uint32_t>(c1 - c0)};
     uint8_t* __restrict__ out = a.out + lo;

@@ -436,6 +436,85 @@ hipError_t launch_batch_bits(const BatchBitsArgs& a, hipStream_t s);
 hipError_t launch_batch_pack(const BatchPackArgs& a, hipStream_t s);
 hipError_t launch_batch_decode(const BatchDecodeArgs& a, hipStream_t s);
 
+// The batch as CompressData::to_bytes blobs (comp.rs:279-300) and back
+// (try_from_bytes, comp.rs:128-184), and the parallel count + restart index of
+// streams that came without one (batch_container.hip). Blob s is
+// blobs[blob_off[s], blob_off[s + 1]): [tree_pad << 4 | data_pad][u32 BE tree
+// bytes][tree bytes][compressed bytes]. A stream's segment entries are
+// seg[batch_seg_offset(comp_off[s], s) + k] = the first code boundary at or
+// past bit k * kBatchSegBits | the letters before it << 32.
+enum : uint32_t {
+    kBatchFromBytes = 5, kBatchDeep = 7, kBatchEmptyComp = 14, kBatchPadding = 15, kBatchTreeLen = 16
+};  // = HUFF_E_FROM_BYTES, HUFF_E_CODE_TOO_LONG, HUFF_E_EMPTY_COMP, HUFF_E_PADDING, HUFF_E_TREE_LEN
+struct BatchBlobArgs {
+    const uint8_t* tree_bits;     // [nstreams][tree_stride]
+    uint32_t tree_stride;
+    const uint32_t* tree_nbits;
+    const uint8_t* comp;
+    const uint64_t* comp_off;
+    const uint64_t* bits;         // unused by the offsets
+    const uint32_t* status;       // a stream that is not kBatchOk owns no blob bytes
+    uint32_t nstreams;
+    uint64_t* blob_off;           // [nstreams + 1]: written by the offsets, read by to_bytes
+    uint8_t* out;
+    uint64_t out_cap;
+};
+struct BatchParseArgs {
+    const uint8_t* blobs;
+    const uint64_t* blob_off;
+    uint32_t nstreams;
+    uint8_t* tree_bits;
+    uint32_t tree_stride;         // >= kTreeBitsMaxBytes
+    uint32_t* tree_nbits;
+    uint64_t* codes;              // TreeBatchArgs::codes' format
+    uint32_t* max_len;
+    uint64_t* payload_begin;      // [nstreams]: the first compressed byte, absolute in blobs
+    uint64_t* bits;
+    uint64_t* comp_off;           // [nstreams + 1]: exclusive scan of the payload bytes of the kBatchOk streams
+    uint32_t* status;
+};
+struct BatchUnwrapArgs {
+    const uint8_t* blobs;
+    const uint64_t* payload_begin;
+    const uint64_t* comp_off;
+    const uint32_t* status;
+    uint32_t nstreams;
+    uint8_t* comp;
+    uint64_t comp_cap;
+};
+struct BatchCountArgs {
+    const uint8_t* comp;
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint64_t* codes;
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    uint64_t* seg;
+    uint64_t seg_cap;
+    uint64_t* counts;             // [nstreams]: letters of the stream (0 unless kBatchOk)
+    uint32_t* status;             // status_in passed through, kBatchOk or kBatchCorrupt
+};
+struct BatchIndexArgs {
+    const uint8_t* comp;
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint64_t* codes;
+    const uint64_t* seg;
+    uint64_t seg_cap;
+    const uint64_t* off;          // the letters' offsets: the scan of BatchCountArgs::counts
+    const uint64_t* idx_off;      // the scan of ceil(counts / kIdx)
+    uint32_t* status;             // in and out: kBatchCorrupt where seg and off disagree
+    uint32_t nstreams;
+    uint32_t* sub;
+    uint64_t sub_cap;
+};
+hipError_t launch_batch_blob_offsets(const BatchBlobArgs& a, hipStream_t s);
+hipError_t launch_batch_to_bytes(const BatchBlobArgs& a, hipStream_t s);
+hipError_t launch_batch_parse(const BatchParseArgs& a, hipStream_t s);
+hipError_t launch_batch_unwrap(const BatchUnwrapArgs& a, hipStream_t s);
+hipError_t launch_batch_count(const BatchCountArgs& a, hipStream_t s);
+hipError_t launch_batch_index(const BatchIndexArgs& a, hipStream_t s);
+
 // codes longer than kLongMaxLen (deep.hip): up to 255 bits, kDeepWords
 // left-aligned words per letter
 constexpr uint32_t kDeepWords = 8;

@@ -11,6 +11,7 @@
 #include <random>
 #include <vector>
 
+#include "host/batch_container.hpp"
 #include "host/dectables.hpp"
 #include "host/huff_coding.hpp"
 #include "host/rust_heap.hpp"
@@ -523,7 +524,39 @@ static void dec_tables_fibonacci() {
     CHECK(f.chain == (d.maxdepth - d.bits + 7) / 8 && f.chain >= 6);
 }
 
+// huff_batch_seg_entries' layout (host/batch_container.hpp): every stream's
+// segments fit between its offset and the next stream's, and the last stream's
+// below the total, for stream sizes of every shape
+static void batch_seg_layout() {
+    std::mt19937_64 rng(7);
+    auto check = [&](const std::vector<uint64_t>& bytes) {
+        uint64_t c = 0, need = 0;
+        for (size_t s = 0; s < bytes.size(); ++s) {
+            // the fewest pad bits (0) give the most segments
+            const uint64_t nseg = (bytes[s] * 8 + kBatchSegBits - 1) / kBatchSegBits;
+            need += nseg;
+            CHECK(batch_seg_offset(c, s) + nseg <= batch_seg_offset(c + bytes[s], s + 1));
+            c += bytes[s];
+        }
+        CHECK(batch_seg_entries(c, bytes.size()) >= need);
+        CHECK(batch_seg_entries(c, bytes.size()) == batch_seg_offset(c, bytes.size()));
+    };
+    check({});
+    check(std::vector<uint64_t>(1000, 0));
+    check(std::vector<uint64_t>(1000, 1));
+    check({(1ull << 29) - 1});  // one stream at the 2^32-bit limit
+    check({0, (1ull << 29) - 1, 0, 1});
+    for (int it = 0; it < 200; ++it) {
+        std::vector<uint64_t> b(rng() % 300);
+        for (auto& x : b) x = rng() % 4 == 0 ? rng() % 3 : rng() % 70000;
+        check(b);
+    }
+    CHECK(batch_seg_entries(0, 0) == 0);
+    CHECK(batch_seg_entries(~0ull, 0xFFFFFFFFu) > 0);  // no overflow at the arguments' limits
+}
+
 int main() {
+    batch_seg_layout();
     dec_tables_one_letter();
     dec_tables_two_letters();
     dec_tables_all8();

@@ -107,6 +107,13 @@ SIGNATURES = [
     ("huff_batch_bits", i, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
     ("huff_batch_pack", i, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, sz]),
     ("huff_batch_decode", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]),
+    ("huff_batch_blob_offsets", i, [vp, vp, vp, vp, C.c_uint32, vp]),
+    ("huff_batch_to_bytes", i, [vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, sz]),
+    ("huff_batch_parse", i, [vp, vp, vp, C.c_uint32, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+    ("huff_batch_unwrap", i, [vp, vp, vp, vp, vp, C.c_uint32, vp, sz]),
+    ("huff_batch_seg_entries", sz, [sz, C.c_uint32]),
+    ("huff_batch_count", i, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, vp]),
+    ("huff_batch_index", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz]),
     ("huff_comm_unique_id", i, [vp]),
     ("huff_comm_init", i, [vp, vp, i, i, C.POINTER(vp)]),
     ("huff_comm_free", None, [vp]),

@@ -23,6 +23,29 @@ or in one call each way:
     c = compress_batch(ctx, data_u8, offsets_i64)          # BatchCompressed
     letters, status = decompress_batch(ctx, c)
 
+A batch leaves and enters the process as the reference's containers
+(CompressData::to_bytes / try_from_bytes, comp.rs:279-300, 128-184), one blob
+per stream, tightly concatenated:
+
+    blobs, blob_off = c.to_bytes(ctx)                      # blobs[blob_off[s]: blob_off[s + 1]]
+    c = BatchCompressed.from_bytes(ctx, blobs, blob_off)   # also blobs the reference CPU wrote
+    letters, status = decompress_batch(ctx, c)
+
+from_bytes knows no letter counts: it is
+
+    p = batch_parse(ctx, blobs, blob_off)                  # ParsedBlobs: trees, bits, comp_offsets, payload_begin
+    batch_unwrap(ctx, blobs, p, comp)                      # the tight layout; ncomp = p.comp_offsets[-1] bytes
+    seg = torch.empty(batch_seg_entries(ncomp, S), dtype=torch.int64, device=...)
+    counts, status = batch_count(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, p.status, seg)
+    offsets, idx_off = scans of counts and ceil(counts / 64)
+    batch_index(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, seg, offsets, idx_off, status, sub)
+
+after which the stream is one that batch_pack wrote. batch_count holds one code
+per letter (the code table's row): a foreign stream that uses the earlier,
+shadowed leaf of a letter its tree holds twice gets E_CORRUPT (no encoder emits
+that code; the single-stream decoder tables every leaf), and so does a stream
+whose last code is cut off, where the reference drops it silently.
+
 The codes row of a stream need not come from its own histogram: one tree's
 row may be given to every stream. A stream that cannot be coded gets a status
 (E_EMPTY_WEIGHTS, E_CODE_TOO_LONG, E_MISSING_LETTER, E_INVALID_ARG for 2^32
@@ -94,8 +117,13 @@ E_INVALID_ARG = _lib.E_INVALID_ARG
 E_MISSING_LETTER = _lib.E_MISSING_LETTER
 E_BUFFER_TOO_SMALL = _lib.E_BUFFER_TOO_SMALL
 E_CORRUPT = _lib.E_CORRUPT
+E_FROM_BYTES = _lib.E_FROM_BYTES
+E_TREE_LEN = _lib.E_TREE_LEN
+E_EMPTY_COMP = _lib.E_EMPTY_COMP
+E_PADDING = _lib.E_PADDING
 
 IDX = 64  # letters per restart index entry
+SEG_BITS = 256  # HUFF_BATCH_SEG_BITS: bits per segment of batch_count's walk
 
 
 def _p(t):
@@ -187,6 +215,137 @@ def batch_decode(ctx, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torc
     return status
 
 
+def _inside(offsets: torch.Tensor, n: int, what: str):
+    """every offset in [0, n]: one device reduction, one host read"""
+    if offsets.numel():
+        ok = (offsets.min() >= 0) & (offsets.max() <= n)
+        if not bool(ok.item()):
+            raise ValueError(f"{what} must lie inside their buffer")
+
+
+def batch_blob_offsets(ctx, tree_nbits: torch.Tensor, comp_offsets: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """huff_batch_blob_offsets: [S + 1] int64, the exclusive scan of the blob
+    sizes (0 for a stream whose status is not 0)"""
+    ns = status.numel()
+    _dev(tree_nbits, torch.int32, (ns,))
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(status, torch.int32, (ns,))
+    blob_offsets = torch.zeros(ns + 1, dtype=torch.int64, device=status.device)
+    _check(load().huff_batch_blob_offsets(ctx.h, _p(tree_nbits), _p(comp_offsets), _p(status), ns, _p(blob_offsets)))
+    return blob_offsets
+
+
+def batch_to_bytes(ctx, trees: "BatchTrees", comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor,
+                   status: torch.Tensor, blob_offsets: torch.Tensor, out: torch.Tensor) -> None:
+    """huff_batch_to_bytes into out (u8, its numel is the capacity); raises
+    HuffError (E_BUFFER_TOO_SMALL) with nothing written if it is short"""
+    ns = status.numel()
+    _dev(trees.tree_bits, torch.uint8)
+    assert trees.tree_bits.dim() == 2 and trees.tree_bits.shape[0] == ns
+    _dev(trees.tree_nbits, torch.int32, (ns,))
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(status, torch.int32, (ns,))
+    _dev(blob_offsets, torch.int64, (ns + 1,))
+    _dev(out, torch.uint8)
+    _inside(comp_offsets, comp.numel(), "comp_offsets")
+    _check(load().huff_batch_to_bytes(ctx.h, _p(trees.tree_bits), trees.tree_bits.shape[1], _p(trees.tree_nbits),
+                                      _p(comp), _p(comp_offsets), _p(bits), _p(status), ns, _p(blob_offsets), _p(out),
+                                      out.numel()))
+
+
+@dataclass
+class ParsedBlobs:
+    trees: BatchTrees             # status: 0, E_FROM_BYTES, E_TREE_LEN, E_EMPTY_COMP, E_PADDING, E_CODE_TOO_LONG, E_INVALID_ARG
+    payload_begin: torch.Tensor   # [S] int64: the first compressed byte of stream s in blobs
+    bits: torch.Tensor            # [S] int64
+    comp_offsets: torch.Tensor    # [S + 1] int64: the tight layout of the payloads
+    status: torch.Tensor          # [S] int32 (trees.status)
+
+
+def batch_parse(ctx, blobs: torch.Tensor, blob_offsets: torch.Tensor) -> ParsedBlobs:
+    """huff_batch_parse: try_from_bytes of blobs[blob_offsets[s]:blob_offsets[s + 1]] for every s"""
+    _dev(blobs, torch.uint8)
+    _dev(blob_offsets, torch.int64)
+    ns = blob_offsets.numel() - 1
+    assert ns >= 0
+    _inside(blob_offsets, blobs.numel(), "blob_offsets")
+    dev = blob_offsets.device
+    t = BatchTrees(torch.zeros((ns, TREE_BITS_MAX_BYTES), dtype=torch.uint8, device=dev),
+                   torch.zeros(ns, dtype=torch.int32, device=dev), torch.empty((ns, 256), dtype=torch.int64, device=dev),
+                   torch.zeros(ns, dtype=torch.int32, device=dev), torch.zeros(ns, dtype=torch.int32, device=dev))
+    payload_begin = torch.zeros(ns, dtype=torch.int64, device=dev)
+    bits = torch.zeros(ns, dtype=torch.int64, device=dev)
+    comp_offsets = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
+    _check(load().huff_batch_parse(ctx.h, _p(blobs), _p(blob_offsets), ns, _p(t.tree_bits), TREE_BITS_MAX_BYTES,
+                                   _p(t.tree_nbits), _p(t.codes), _p(t.max_len), _p(payload_begin), _p(bits),
+                                   _p(comp_offsets), _p(t.status)))
+    return ParsedBlobs(t, payload_begin, bits, comp_offsets, t.status)
+
+
+def batch_unwrap(ctx, blobs: torch.Tensor, p: ParsedBlobs, comp: torch.Tensor) -> None:
+    """huff_batch_unwrap: the payloads into comp (u8, its numel is the capacity) at p.comp_offsets"""
+    _dev(blobs, torch.uint8)
+    _dev(comp, torch.uint8)
+    ns = p.status.numel()
+    _check(load().huff_batch_unwrap(ctx.h, _p(blobs), _p(p.payload_begin), _p(p.comp_offsets), _p(p.status), ns,
+                                    _p(comp), comp.numel()))
+
+
+def batch_seg_entries(total_comp_bytes: int, nstreams: int) -> int:
+    """huff_batch_seg_entries: the int64 entries of scratch batch_count and batch_index need"""
+    return int(load().huff_batch_seg_entries(total_comp_bytes, nstreams))
+
+
+def batch_count(ctx, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor, codes: torch.Tensor,
+                status_in: torch.Tensor, seg: torch.Tensor):
+    """huff_batch_count: (counts [S] int64, status [S] int32); seg (int64
+    scratch of batch_seg_entries entries) is filled for batch_index"""
+    ns = status_in.numel()
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(codes, torch.int64, (ns, 256))
+    _dev(status_in, torch.int32, (ns,))
+    _dev(seg, torch.int64)
+    _inside(comp_offsets, comp.numel(), "comp_offsets")
+    counts = torch.zeros(ns, dtype=torch.int64, device=status_in.device)
+    status = torch.zeros(ns, dtype=torch.int32, device=status_in.device)
+    _check(load().huff_batch_count(ctx.h, _p(comp), _p(comp_offsets), _p(bits), _p(codes), _p(status_in), ns, _p(seg),
+                                   seg.numel(), _p(counts), _p(status)))
+    return counts, status
+
+
+def batch_index(ctx, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor, codes: torch.Tensor,
+                seg: torch.Tensor, offsets: torch.Tensor, index_offsets: torch.Tensor, status: torch.Tensor,
+                sub: torch.Tensor) -> None:
+    """huff_batch_index into sub (int32 holding u32 offsets, its numel is the
+    capacity); status is updated in place"""
+    ns = status.numel()
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(codes, torch.int64, (ns, 256))
+    _dev(seg, torch.int64)
+    _dev(offsets, torch.int64, (ns + 1,))
+    _dev(index_offsets, torch.int64, (ns + 1,))
+    _dev(status, torch.int32, (ns,))
+    _dev(sub, torch.int32)
+    _inside(comp_offsets, comp.numel(), "comp_offsets")
+    _inside(index_offsets, sub.numel(), "index_offsets")
+    if seg.numel() < batch_seg_entries(comp.numel(), ns):
+        raise ValueError("seg is smaller than batch_seg_entries(comp.numel(), nstreams)")
+    _check(load().huff_batch_index(ctx.h, _p(comp), _p(comp_offsets), _p(bits), _p(codes), _p(seg), _p(offsets),
+                                   _p(index_offsets), _p(status), ns, _p(sub), sub.numel()))
+
+
+def _scan(x: torch.Tensor) -> torch.Tensor:
+    out = torch.zeros(x.numel() + 1, dtype=torch.int64, device=x.device)
+    torch.cumsum(x, 0, out=out[1:])
+    return out
+
+
 @dataclass
 class BatchCompressed:
     comp: torch.Tensor           # u8: the streams' compressed bytes, tightly concatenated
@@ -197,6 +356,34 @@ class BatchCompressed:
     trees: BatchTrees
     status: torch.Tensor         # [S] int32
     offsets: torch.Tensor        # [S + 1] int64: the letters' offsets
+
+    def to_bytes(self, ctx):
+        """(blobs u8, blob_offsets [S + 1] int64): every stream whose status is
+        0 as CompressData::to_bytes writes it (comp.rs:279-300); the others own
+        no bytes. Two calls and one host read of the total."""
+        blob_offsets = batch_blob_offsets(ctx, self.trees.tree_nbits, self.comp_offsets, self.status)
+        blobs = torch.empty(int(blob_offsets[-1].item()), dtype=torch.uint8, device=self.comp.device)
+        batch_to_bytes(ctx, self.trees, self.comp, self.comp_offsets, self.bits, self.status, blob_offsets, blobs)
+        return blobs, blob_offsets
+
+    @staticmethod
+    def from_bytes(ctx, blobs: torch.Tensor, blob_offsets: torch.Tensor) -> "BatchCompressed":
+        """try_from_bytes (comp.rs:128-184) of every blob, then the letter
+        counts and the restart index by the parallel walk: parse, unwrap,
+        count, index, and two host reads of totals. decompress_batch takes the
+        result; a blob that does not parse, or whose stream is corrupt, has
+        its status and no letters."""
+        p = batch_parse(ctx, blobs, blob_offsets)
+        ns = p.status.numel()
+        comp = torch.empty(int(p.comp_offsets[-1].item()), dtype=torch.uint8, device=blobs.device)
+        batch_unwrap(ctx, blobs, p, comp)
+        seg = torch.empty(batch_seg_entries(comp.numel(), ns), dtype=torch.int64, device=blobs.device)
+        counts, status = batch_count(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, p.status, seg)
+        offsets = _scan(counts)
+        index_offsets = _scan((counts + (IDX - 1)) // IDX)
+        sub = torch.empty(int(index_offsets[-1].item()), dtype=torch.int32, device=blobs.device)
+        batch_index(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, seg, offsets, index_offsets, status, sub)
+        return BatchCompressed(comp, p.comp_offsets, p.bits, sub, index_offsets, p.trees, status, offsets)
 
 
 def compress_batch(ctx, data: torch.Tensor, offsets: torch.Tensor) -> BatchCompressed:

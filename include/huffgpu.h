@@ -388,6 +388,90 @@ int huff_batch_decode(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_co
                       const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out,
                       uint32_t* d_status);
 
+/* The batch as containers and back (device pointers unless named h_,
+ * synchronous, on the context's stream). Stream s's blob is
+ * CompressData::to_bytes of it alone (comp.rs:279-300):
+ *   [tree_pad << 4 | data_pad][u32 BE tree bytes][tree bytes][compressed bytes]
+ * with tree_pad = (8 - tree_nbits % 8) % 8 and data_pad = (8 - bits % 8) % 8;
+ * the blobs lie tightly at d_blob_offsets[s] (nstreams + 1 entries).
+ *  huff_batch_blob_offsets: the exclusive scan of the blob sizes: 5 +
+ *                     ceil(d_tree_nbits[s] / 8) + the stream's compressed
+ *                     bytes for a stream whose d_status is HUFF_OK, 0 for any
+ *                     other.
+ *  huff_batch_to_bytes: writes every blob; reads the total back first and
+ *                     returns HUFF_E_BUFFER_TOO_SMALL, nothing written, if
+ *                     out_cap is short. Every output byte has one writer;
+ *                     nothing outside a stream's own blob is touched.
+ *  huff_batch_parse:  CompressData::try_from_bytes (comp.rs:128-184) of every
+ *                     blob, HuffTree::try_from_bin (tree_inner.rs:522-604) on
+ *                     the device: the tree bits (zero tail) to d_tree_bits + s
+ *                     * tree_stride, d_tree_nbits, d_codes and d_max_len as
+ *                     huff_batch_trees writes them (the later leaf of a
+ *                     repeated letter gives its code, as read_codes does),
+ *                     d_payload_begin[s] = the first compressed byte, absolute
+ *                     in d_blobs, d_bits[s] = 8 * payload bytes - data_pad,
+ *                     d_comp_offsets = the exclusive scan of the payload bytes
+ *                     (the tight layout of the calls above). d_status[s] is
+ *                     huff_cd_try_from_bytes's for the blob alone
+ *                     (HUFF_E_FROM_BYTES, HUFF_E_TREE_LEN, HUFF_E_EMPTY_COMP,
+ *                     HUFF_E_PADDING, in the reference's order), or
+ *                     HUFF_E_CODE_TOO_LONG (a code over 56 bits: its d_codes
+ *                     entry is 0, the tree bits are still copied), or
+ *                     HUFF_E_INVALID_ARG (a tree of more than
+ *                     HUFF_TREE_BITS_MAX_BYTES bytes, or 2^32 payload bits or
+ *                     more: huff_cd_try_from_bytes takes such a blob). A stream
+ *                     that is not HUFF_OK has 0 bits and owns 0 bytes.
+ *  huff_batch_unwrap: copies the payloads to d_comp + d_comp_offsets[s]
+ *                     (HUFF_E_BUFFER_TOO_SMALL, nothing written, if comp_cap is
+ *                     short).
+ *  huff_batch_seg_entries: host only: the u64 entries of d_seg that the next
+ *                     two calls need for total_comp_bytes (d_comp_offsets[
+ *                     nstreams]) and nstreams; at least one entry per started
+ *                     HUFF_BATCH_SEG_BITS bits of every stream.
+ *  huff_batch_count:  d_counts[s] = the letters decompress (comp.rs:487-519)
+ *                     yields for stream s, by a speculative, self-correcting
+ *                     parallel walk whose result is the serial walk's; d_seg
+ *                     gets each 256-bit segment's first code boundary and the
+ *                     letters before it. d_status[s] = d_status_in[s] if that
+ *                     is not HUFF_OK, else HUFF_OK, or HUFF_E_CORRUPT: a window
+ *                     matches no code, or the last code crosses d_bits[s]
+ *                     (huff_batch_decode's rule; the reference drops a trailing
+ *                     partial code silently). d_codes holds one code per
+ *                     letter: a stream that uses the earlier, shadowed leaf of
+ *                     a letter its tree holds twice is HUFF_E_CORRUPT here
+ *                     (no encoder emits that code; huff_decompress tables every
+ *                     leaf). HUFF_E_BUFFER_TOO_SMALL if seg_cap is short.
+ *  huff_batch_index:  from d_seg and the scans of d_counts (d_offsets) and of
+ *                     ceil(d_counts / 64) (d_index_offsets): d_sub[
+ *                     d_index_offsets[s] + j] = the bit offset of letter 64 j,
+ *                     huff_batch_pack's index. d_status is read and updated:
+ *                     HUFF_E_CORRUPT where d_seg and the offsets disagree.
+ *                     HUFF_E_BUFFER_TOO_SMALL, nothing written, if sub_cap is
+ *                     short. huff_batch_decode then takes the stream as one
+ *                     that huff_batch_pack wrote. */
+int huff_batch_blob_offsets(huff_ctx* ctx, const uint32_t* d_tree_nbits, const uint64_t* d_comp_offsets,
+                            const uint32_t* d_status, uint32_t nstreams, uint64_t* d_blob_offsets);
+int huff_batch_to_bytes(huff_ctx* ctx, const uint8_t* d_tree_bits, size_t tree_stride, const uint32_t* d_tree_nbits,
+                        const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                        const uint32_t* d_status, uint32_t nstreams, const uint64_t* d_blob_offsets, uint8_t* d_out,
+                        size_t out_cap);
+int huff_batch_parse(huff_ctx* ctx, const uint8_t* d_blobs, const uint64_t* d_blob_offsets, uint32_t nstreams,
+                     uint8_t* d_tree_bits, size_t tree_stride, uint32_t* d_tree_nbits, uint64_t* d_codes,
+                     uint32_t* d_max_len, uint64_t* d_payload_begin, uint64_t* d_bits, uint64_t* d_comp_offsets,
+                     uint32_t* d_status);
+int huff_batch_unwrap(huff_ctx* ctx, const uint8_t* d_blobs, const uint64_t* d_payload_begin,
+                      const uint64_t* d_comp_offsets, const uint32_t* d_status, uint32_t nstreams, uint8_t* d_comp,
+                      size_t comp_cap);
+#define HUFF_BATCH_SEG_BITS 256
+size_t huff_batch_seg_entries(size_t total_comp_bytes, uint32_t nstreams);
+int huff_batch_count(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                     const uint64_t* d_codes, const uint32_t* d_status_in, uint32_t nstreams, uint64_t* d_seg,
+                     size_t seg_cap, uint64_t* d_counts, uint32_t* d_status);
+int huff_batch_index(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets, const uint64_t* d_bits,
+                     const uint64_t* d_codes, const uint64_t* d_seg, const uint64_t* d_offsets,
+                     const uint64_t* d_index_offsets, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub,
+                     size_t sub_cap);
+
 /* synthetic inputs generated on the device (not reference functions):
  * kind 0 = uniform bytes, 1 = Zipf(alpha) with cdf[256] (host), 2 = text.
  * Byte i of the stream depends only on (kind, seed, offset + i). */

@@ -13,6 +13,14 @@ whole batched compress and decompress, and beside them the per-stream route
 (one device job per stream: huff_enc_create + huff_enc_compress, then
 huff_enc_decode) timed over --loop-sample streams and extrapolated to the
 batch.
+
+--container adds the batch's containers on the same two inputs: kernel times
+of huff_batch_blob_offsets / to_bytes / parse / unwrap / count / index, of the
+indexed decode through the index that count + index built, and, in the same
+job, of the unchanged serial index-free decode (huff_batch_decode without an
+index, given the true letter counts) that count + index + indexed decode
+replace; the wall time of to_bytes and of from_bytes + decompress_batch; and
+k_hist_batch, which reads the same bytes once, beside them.
 """
 import argparse
 import json
@@ -112,6 +120,70 @@ def codec(ctx, kind, S, L, iters, loop_sample):
     return res
 
 
+def container(ctx, kind, S, L, iters):
+    """the containers of S streams of L bytes of `kind`: out, back in without
+    the letter counts, and the serial index-free decode for comparison"""
+    from huff_coding import device
+
+    n = S * L
+    data = torch.empty(n, dtype=torch.uint8, device="cuda")
+    device.generate(ctx, kind, 11, data.data_ptr(), n, cdf=device.zipf_cdf(1.2) if kind == "zipf" else None)
+    offs = torch.arange(0, S + 1, device="cuda", dtype=torch.int64) * L
+    c = batch.compress_batch(ctx, data, offs)
+    blobs, boff = c.to_bytes(ctx)  # warm-up of every call, and the check that what is timed is right
+    f = batch.BatchCompressed.from_bytes(ctx, blobs, boff)
+    out, st = batch.decompress_batch(ctx, f)
+    torch.cuda.synchronize()
+    assert int((c.status != 0).sum()) == 0 and int((st != 0).sum()) == 0 and torch.equal(out, data)
+    assert torch.equal(f.sub, c.sub) and torch.equal(f.offsets, offs) and torch.equal(f.comp, c.comp)
+    p = batch.batch_parse(ctx, blobs, boff)
+    comp = torch.empty_like(c.comp)
+    seg = torch.empty(batch.batch_seg_entries(comp.numel(), S), dtype=torch.int64, device="cuda")
+    sub = torch.empty_like(c.sub)
+    blobs2 = torch.empty_like(blobs)
+    ctx.set_timing(True)
+    ctx.reset_timing()
+    for _ in range(iters):
+        batch.batch_hist(ctx, data, offs)
+        b2 = batch.batch_blob_offsets(ctx, c.trees.tree_nbits, c.comp_offsets, c.status)
+        batch.batch_to_bytes(ctx, c.trees, c.comp, c.comp_offsets, c.bits, c.status, b2, blobs2)
+        p = batch.batch_parse(ctx, blobs, boff)
+        batch.batch_unwrap(ctx, blobs, p, comp)
+        counts, status = batch.batch_count(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, p.status, seg)
+        batch.batch_index(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, seg, f.offsets, f.index_offsets, status, sub)
+        batch.batch_decode(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, sub, f.index_offsets, f.offsets, status, out)
+        batch.batch_decode(ctx, comp, p.comp_offsets, p.bits, p.trees.codes, None, None, offs, status, out)
+    torch.cuda.synchronize()
+    assert torch.equal(out, data) and torch.equal(sub, c.sub) and torch.equal(blobs2, blobs)
+    res = {"kind": kind, "comp_ratio": round(c.comp.numel() / n, 4), "blob_bytes": blobs.numel(),
+           "seg_bits": batch.SEG_BITS if not os.environ.get("HUFF_LIB_AB") else os.environ["HUFF_LIB_AB"]}
+    names = ("hist_batch", "batch_blob_offsets", "batch_to_bytes", "batch_parse", "batch_unwrap", "batch_count",
+             "batch_index", "batch_decode", "batch_decode_noindex")
+    for k in names:
+        ms, cnt = ctx.kernel_time(k)
+        res[k + "_ms"] = round(ms / cnt, 4)
+        res[k + "_GBps"] = round(n / (ms / cnt * 1e-3) / 1e9, 1)
+    ctx.set_timing(False)
+    par = res["batch_count_ms"] + res["batch_index_ms"] + res["batch_decode_ms"]
+    res["count_index_decode_ms"] = round(par, 4)
+    res["speedup_over_serial_index_free"] = round(res["batch_decode_noindex_ms"] / par, 2)
+    wt, wf = [], []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        blobs, boff = c.to_bytes(ctx)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        f = batch.BatchCompressed.from_bytes(ctx, blobs, boff)
+        batch.decompress_batch(ctx, f)
+        torch.cuda.synchronize()
+        wt.append(t1 - t0)
+        wf.append(time.perf_counter() - t1)
+    res["to_bytes_wall_ms"] = round(min(wt) * 1e3, 3)
+    res["from_bytes_decompress_wall_ms"] = round(min(wf) * 1e3, 3)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=10000)
@@ -119,6 +191,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cpu-sample", type=int, default=500, help="streams built on the host for comparison")
     ap.add_argument("--codec", action="store_true", help="also the batched codec and the per-stream loop")
+    ap.add_argument("--container", action="store_true", help="also the batch's containers and the parallel count")
     ap.add_argument("--loop-sample", type=int, default=200, help="streams of the per-stream loop")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -161,6 +234,9 @@ def main():
     if args.codec:
         ctx.set_timing(False)
         res["codec"] = [codec(ctx, kind, S, L, args.iters, args.loop_sample) for kind in ("uniform", "zipf")]
+    if args.container:
+        ctx.set_timing(False)
+        res["container"] = [container(ctx, kind, S, L, args.iters) for kind in ("uniform", "zipf")]
     print(json.dumps(res), flush=True)
 
 
