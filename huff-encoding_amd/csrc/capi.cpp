@@ -674,6 +674,43 @@ int huff_batch_decode(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_co
     });
 }
 
+int huff_batch_decode_ranges(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                             const uint64_t* d_bits, const uint64_t* d_codes, const uint32_t* d_sub,
+                             const uint64_t* d_index_offsets, const uint64_t* d_offsets,
+                             const uint32_t* d_status_in, uint32_t nstreams, const uint32_t* d_req_stream,
+                             const uint64_t* d_req_first, const uint64_t* d_req_count,
+                             const uint64_t* d_req_out_begin, uint32_t nreq, uint8_t* d_out, uint32_t* d_req_status) {
+    if (!ctx || (nreq && (!d_req_stream || !d_req_first || !d_req_count || !d_req_out_begin || !d_req_status ||
+                          (nstreams && (!d_comp_offsets || !d_bits || !d_codes || !d_index_offsets || !d_offsets ||
+                                        !d_status_in)))))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (nreq && !d_sub) return fail(HUFF_E_INVALID_ARG, "a letter range needs the restart index (d_sub)");
+    if (nreq == 0) return HUFF_OK;
+    return guarded([&]() -> huff::Status {
+        HUFF_TRY(ctx->activate());
+        huff::dev::BatchRangesArgs a{};
+        a.comp = d_comp;
+        a.comp_off = d_comp_offsets;
+        a.bits = d_bits;
+        a.codes = d_codes;
+        a.sub = d_sub;
+        a.idx_off = d_index_offsets;
+        a.off = d_offsets;
+        a.status_in = d_status_in;
+        a.nstreams = nstreams;
+        a.req_stream = d_req_stream;
+        a.req_first = d_req_first;
+        a.req_count = d_req_count;
+        a.out_begin = d_req_out_begin;
+        a.nreq = nreq;
+        a.out = d_out;
+        a.status = d_req_status;
+        HUFF_TRY(ctx->timed("batch_decode_ranges",
+                            [&] { return huff::dev::launch_batch_decode_ranges(a, ctx->stream); }));
+        return ctx->sync();
+    });
+}
+
 namespace {
 
 // one u64 of device memory, read on the context's stream

@@ -26,6 +26,11 @@
 //                  [kIdx j, kIdx j + kIdx) from sub[j] and must end at
 //                  sub[j + 1] (the last lane: at bits[s]). Without an index
 //                  one lane walks the stream.
+//  k_batch_decode_ranges  one workgroup per request (stream, first letter,
+//                  count, output position): the same table, one lane per
+//                  kIdx-letter block the range touches, each block decoded
+//                  whole under k_batch_decode's rule and only the wanted
+//                  letters stored.
 #include "batch_lut.hpp"
 #include "pack_emit.hpp"
 
@@ -270,12 +275,14 @@ constexpr uint32_t kBdStageBytes = kBThreads * kIdx * 9 / 8;
 
 // cnt symbols from bit `start`, which must end exactly at bit `end`; the
 // letters go to out[0, cnt) in 16-B pieces. False: a window without a code, or
-// a code crossing `end`, or an end other than `end`.
-template <class Src>
+// a code crossing `end`, or an end other than `end`. CLIP (k_batch_decode_ranges):
+// all cnt symbols are decoded, but only the letters [skip, skip + keep) are
+// stored, at out[0, keep); a piece that lies wholly inside still leaves as 16 B.
+template <bool CLIP, class Src>
 __device__ __forceinline__ bool batch_decode_run(const Src& src, uint32_t start, uint32_t end, uint32_t cnt,
                                                  uint8_t* __restrict__ out, const uint16_t* __restrict__ lut,
                                                  const uint64_t* __restrict__ tab, const uint8_t* __restrict__ longl,
-                                                 uint32_t nlong) {
+                                                 uint32_t nlong, uint32_t skip = 0, uint32_t keep = 0) {
     if (start > end) return false;
     uint32_t pos = start, wi = start >> 5;
     uint64_t buf = ((static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1)) << (start & 31);
@@ -312,9 +319,14 @@ __device__ __forceinline__ bool batch_decode_run(const Src& src, uint32_t start,
             z = __builtin_amdgcn_alignbit(w, z, 8);
             w = (w >> 8) | (letter << 24);
         }
-        if (m == 16) {
+        bool whole = m == 16;
+        if constexpr (CLIP) whole = whole && done >= skip && done + 16 - skip <= keep;
+        if (whole) {
             const uint4 v = make_uint4(x, y, z, w);
-            __builtin_memcpy(out + done, &v, 16);  // any alignment
+            if constexpr (CLIP)
+                __builtin_memcpy(out + (done - skip), &v, 16);
+            else
+                __builtin_memcpy(out + done, &v, 16);  // any alignment
         } else {
             for (uint32_t k = m; k < 16; ++k) {
                 x = __builtin_amdgcn_alignbit(y, x, 8);
@@ -323,7 +335,11 @@ __device__ __forceinline__ bool batch_decode_run(const Src& src, uint32_t start,
                 w >>= 8;
             }
             for (uint32_t k = 0; k < m; ++k) {
-                out[done + k] = static_cast<uint8_t>(x);
+                if constexpr (CLIP) {
+                    if (done + k - skip < keep) out[done + k - skip] = static_cast<uint8_t>(x);  // below skip: wraps
+                } else {
+                    out[done + k] = static_cast<uint8_t>(x);
+                }
                 x = __builtin_amdgcn_alignbit(y, x, 8);
                 y = __builtin_amdgcn_alignbit(z, y, 8);
                 z = __builtin_amdgcn_alignbit(w, z, 8);
@@ -403,16 +419,115 @@ __global__ __launch_bounds__(TH) void k_batch_decode(BatchDecodeArgs a) {
             const uint32_t cnt = j + 1 < nblk ? kIdx : static_cast<uint32_t>(n - j * kIdx);
             const bool sane = (j != 0 || start == 0) && end <= end_all;
             if (staged)
-                ok &= sane && batch_decode_run(BatchSrcLds{cst, b0, span}, start, end, cnt, out + j * kIdx, lut, tab, longl, nl);
+                ok &= sane && batch_decode_run<false>(BatchSrcLds{cst, b0, span}, start, end, cnt, out + j * kIdx, lut, tab, longl, nl);
             else
-                ok &= sane && batch_decode_run(src, start, end, cnt, out + j * kIdx, lut, tab, longl, nl);
+                ok &= sane && batch_decode_run<false>(src, start, end, cnt, out + j * kIdx, lut, tab, longl, nl);
         }
     } else if (t == 0) {
-        ok = batch_decode_run(src, 0, end_all, static_cast<uint32_t>(n), out, lut, tab, longl, nl);
+        ok = batch_decode_run<false>(src, 0, end_all, static_cast<uint32_t>(n), out, lut, tab, longl, nl);
     }
     if (!ok) bad = 1;
     __syncthreads();
     if (t == 0) a.status[s] = bad ? kBatchCorrupt : kBatchOk;
+}
+
+// ---------------------------------------------------------------------------
+// Letter ranges through the index: one workgroup per request (stream s, letters
+// [f, f + m) -> out + out_begin[r]). Only the kIdx-letter blocks the range
+// touches are decoded, one lane each and each one whole, under k_batch_decode's
+// rule (from sub[j], ending exactly at sub[j + 1], the stream's last block at
+// bits[s]); the head and tail blocks store only their letters inside the range.
+// The request reads sub[j0 .. j1 + 1] and the compressed bytes of its stream
+// only, and writes only its own m bytes. Lanes per request: measured at 64,
+// 128 and 256 ("Letter ranges through the index").
+#ifndef HUFF_BATCH_RANGE_THREADS
+#define HUFF_BATCH_RANGE_THREADS 128
+#endif
+constexpr uint32_t kBrThreads = HUFF_BATCH_RANGE_THREADS;
+static_assert(kBrThreads % 64 == 0 && kBrThreads >= 64 && kBrThreads <= 1024, "whole waves");
+
+template <uint32_t TH>
+__global__ __launch_bounds__(TH) void k_batch_decode_ranges(BatchRangesArgs a) {
+    constexpr uint32_t kStage = TH * kIdx * 9 / 8;  // as kBdStageBytes, for TH lanes
+    __shared__ __attribute__((aligned(16))) uint16_t lut[1u << kBdLutBits];
+    __shared__ uint64_t tab[256];
+    __shared__ uint8_t longl[256], coopl[256];
+    __shared__ uint32_t nlong, ncoop, bad;
+    __shared__ __attribute__((aligned(16))) uint8_t cst[HUFF_BATCH_STAGE ? kStage : 16];
+    const uint32_t r = blockIdx.x, t = threadIdx.x;
+    // every early exit below is workgroup-uniform and comes before any barrier
+    const uint32_t s = a.req_stream[r];
+    const uint64_t f = a.req_first[r], m = a.req_count[r];
+    if (s >= a.nstreams) {
+        if (t == 0) a.status[r] = kBatchInvalid;
+        return;
+    }
+    const uint64_t lo = a.off[s];
+    const uint64_t n = a.off[s + 1] > lo ? a.off[s + 1] - lo : 0;
+    if (f + m < f || f + m > n) {
+        if (t == 0) a.status[r] = kBatchInvalid;
+        return;
+    }
+    const uint32_t st_in = a.status_in[s];
+    if (st_in != kBatchOk || m == 0) {
+        if (t == 0) a.status[r] = st_in;
+        return;
+    }
+    const uint64_t bits = a.bits[s];
+    const uint64_t c0 = a.comp_off[s], c1 = a.comp_off[s + 1];
+    const uint64_t nblk = (n + kIdx - 1) / kIdx;
+    // k_batch_decode's test of the stream's own numbers (n > 0 here)
+    const bool wrong = (bits >> 32) != 0 || c1 < c0 || c1 - c0 != (bits + 7) / 8 || n > bits ||
+                       a.idx_off[s + 1] < a.idx_off[s] || a.idx_off[s + 1] - a.idx_off[s] != nblk;
+    if (wrong) {
+        if (t == 0) a.status[r] = kBatchCorrupt;
+        return;
+    }
+    if (t == 0) bad = 0;
+    batch_build_lut<TH>(a.codes + static_cast<uint64_t>(s) * 256, lut, tab, longl, coopl, &nlong, &ncoop);
+
+    const BatchSrc src{a.comp + c0, static_cast<uint32_t>(c1 - c0)};
+    uint8_t* __restrict__ out = a.out + a.out_begin[r];
+    const uint32_t* __restrict__ sub = a.sub + a.idx_off[s];
+    const uint32_t end_all = static_cast<uint32_t>(bits), nl = nlong;
+    const uint64_t jl = (f + m - 1) / kIdx;  // the last touched block; < nblk
+    bool ok = true;
+    for (uint64_t j0 = f / kIdx; j0 <= jl; j0 += TH) {  // a round: TH lanes, one touched block each
+        const uint64_t j = j0 + t;
+        const uint64_t je = j0 + TH <= jl ? j0 + TH : jl + 1;  // one past the round's last block; <= nblk
+        // the round's compressed bytes through LDS, as in k_batch_decode; both
+        // index entries belong to blocks this request touches
+        const uint32_t b_lo = sub[j0], b_hi = je < nblk ? sub[je] : end_all;
+        uint32_t b0 = 0, span = 0;
+        bool staged = false;
+        if (HUFF_BATCH_STAGE && b_lo <= b_hi && b_hi <= end_all) {
+            b0 = (b_lo >> 3) & ~3u;
+            const uint32_t b1 = ((b_hi + 7) >> 3) + 8 < src.nbytes ? ((b_hi + 7) >> 3) + 8 : src.nbytes;
+            span = b1 - b0;
+            staged = span <= kStage;
+        }
+        if (staged) {  // workgroup-uniform
+            __syncthreads();  // the round before has read its bytes
+            batch_stage<TH>(cst, src.p + b0, span);
+            __syncthreads();
+        }
+        if (j > jl) continue;
+        const uint32_t start = sub[j];
+        const uint32_t end = j + 1 < nblk ? sub[j + 1] : end_all;
+        const uint64_t g = j * kIdx;  // the block's first letter
+        const uint32_t cnt = j + 1 < nblk ? kIdx : static_cast<uint32_t>(n - g);
+        const uint64_t w_lo = f > g ? f : g, w_hi = f + m < g + cnt ? f + m : g + cnt;  // the wanted letters of the block
+        const uint32_t skip = static_cast<uint32_t>(w_lo - g), keep = static_cast<uint32_t>(w_hi - w_lo);
+        const bool sane = (j != 0 || start == 0) && end <= end_all;
+        if (staged)
+            ok &= sane && batch_decode_run<true>(BatchSrcLds{cst, b0, span}, start, end, cnt, out + (w_lo - f), lut, tab,
+                                                 longl, nl, skip, keep);
+        else
+            ok &= sane && batch_decode_run<true>(src, start, end, cnt, out + (w_lo - f), lut, tab, longl, nl, skip, keep);
+    }
+    if (!ok) bad = 1;
+    __syncthreads();
+    if (t == 0) a.status[r] = bad ? kBatchCorrupt : kBatchOk;
 }
 
 }  // namespace
@@ -435,6 +550,12 @@ hipError_t launch_batch_decode(const BatchDecodeArgs& a, hipStream_t s) {
         launch_k(k_batch_decode<kBThreads>, dim3(a.nstreams), dim3(kBThreads), 0, s, a);
     else
         launch_k(k_batch_decode<64>, dim3(a.nstreams), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_decode_ranges(const BatchRangesArgs& a, hipStream_t s) {
+    if (a.nreq == 0) return hipSuccess;
+    launch_k(k_batch_decode_ranges<kBrThreads>, dim3(a.nreq), dim3(kBrThreads), 0, s, a);
     return hipGetLastError();
 }
 

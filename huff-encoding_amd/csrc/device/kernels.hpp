@@ -435,6 +435,29 @@ struct BatchDecodeArgs {
 hipError_t launch_batch_bits(const BatchBitsArgs& a, hipStream_t s);
 hipError_t launch_batch_pack(const BatchPackArgs& a, hipStream_t s);
 hipError_t launch_batch_decode(const BatchDecodeArgs& a, hipStream_t s);
+// Letter ranges of chosen streams through the restart index: request r is
+// letters [req_first[r], req_first[r] + req_count[r]) of stream req_stream[r],
+// stored at out + out_begin[r]; only the kIdx-letter blocks it touches are decoded.
+struct BatchRangesArgs {
+    const uint8_t* comp;
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint64_t* codes;
+    const uint32_t* sub;          // required
+    const uint64_t* idx_off;
+    const uint64_t* off;
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    const uint32_t* req_stream;   // [nreq]
+    const uint64_t* req_first;
+    const uint64_t* req_count;
+    const uint64_t* out_begin;
+    uint32_t nreq;
+    uint8_t* out;
+    uint32_t* status;             // [nreq]: kBatchInvalid (no such stream or range), the stream's status_in,
+                                  // kBatchOk or kBatchCorrupt
+};
+hipError_t launch_batch_decode_ranges(const BatchRangesArgs& a, hipStream_t s);
 
 // The batch as CompressData::to_bytes blobs (comp.rs:279-300) and back
 // (try_from_bytes, comp.rs:128-184), and the parallel count + restart index of

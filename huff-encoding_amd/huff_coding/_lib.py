@@ -107,6 +107,7 @@ SIGNATURES = [
     ("huff_batch_bits", i, [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
     ("huff_batch_pack", i, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, sz]),
     ("huff_batch_decode", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]),
+    ("huff_batch_decode_ranges", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp]),
     ("huff_batch_blob_offsets", i, [vp, vp, vp, vp, C.c_uint32, vp]),
     ("huff_batch_to_bytes", i, [vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, sz]),
     ("huff_batch_parse", i, [vp, vp, vp, C.c_uint32, vp, sz, vp, vp, vp, vp, vp, vp, vp]),

@@ -46,6 +46,24 @@ shadowed leaf of a letter its tree holds twice gets E_CORRUPT (no encoder emits
 that code; the single-stream decoder tables every leaf), and so does a stream
 whose last code is cut off, where the reference drops it silently.
 
+Random access through the restart index: chosen letter ranges of chosen
+streams in one launch that decodes only the 64-letter blocks the ranges touch
+(huff_batch_decode_ranges; any BatchCompressed, also one from from_bytes):
+
+    letters, out_off, st = decompress_ranges(ctx, c, req_stream, req_first, req_count)
+    letters[out_off[r]: out_off[r + 1]]                    # stream req_stream[r], letters [first, first + count)
+    letters, out_off, st = decompress_streams(ctx, c, ids) # whole streams chosen by id
+    st = batch_decode_ranges(ctx, c.comp, c.comp_offsets, c.bits, c.trees.codes, c.sub, c.index_offsets,
+                             c.offsets, c.status, req_stream, req_first, req_count, out_begin, out)
+
+st[r] is E_INVALID_ARG for a stream id or a range outside the batch, the
+stream's own status if that is not 0, E_CORRUPT if a block the range touches
+does not decode from its index entry exactly to the next, else 0; a request
+that is not 0 leaves its slot zero (batch_decode_ranges: unwritten or partly
+written, never a byte outside it). Output ranges that overlap are the caller's
+business. A caller who wants every letter of the batch stays with
+decompress_batch.
+
 The codes row of a stream need not come from its own histogram: one tree's
 row may be given to every stream. A stream that cannot be coded gets a status
 (E_EMPTY_WEIGHTS, E_CODE_TOO_LONG, E_MISSING_LETTER, E_INVALID_ARG for 2^32
@@ -212,6 +230,49 @@ def batch_decode(ctx, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torc
     _check(load().huff_batch_decode(ctx.h, _p(comp), _p(comp_offsets), _p(bits), _p(codes), _p(sub),
                                     _p(index_offsets if sub is not None else None), _p(offsets), _p(status_in), ns,
                                     _p(out), _p(status)))
+    return status
+
+
+def batch_decode_ranges(ctx, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor, codes: torch.Tensor,
+                        sub: torch.Tensor | None, index_offsets: torch.Tensor, offsets: torch.Tensor,
+                        status_in: torch.Tensor, req_stream: torch.Tensor, req_first: torch.Tensor,
+                        req_count: torch.Tensor, out_begin: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """huff_batch_decode_ranges: the letters [req_first[r], req_first[r] +
+    req_count[r]) of stream req_stream[r] to out[out_begin[r]:], decoding only
+    the 64-letter blocks they touch. req_stream is int32 (u32 ids), the other
+    three int64 (u64). Returns the per-request status [R] (int32): see
+    include/huffgpu.h. sub None raises HuffError (E_INVALID_ARG): a range needs
+    the index. Output ranges that overlap are the caller's business."""
+    ns = offsets.numel() - 1
+    assert ns >= 0
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(codes, torch.int64, (ns, 256))
+    _dev(offsets, torch.int64)
+    _dev(status_in, torch.int32, (ns,))
+    _dev(out, torch.uint8)
+    nreq = req_stream.numel()
+    _dev(req_stream, torch.int32, (nreq,))
+    _dev(req_first, torch.int64, (nreq,))
+    _dev(req_count, torch.int64, (nreq,))
+    _dev(out_begin, torch.int64, (nreq,))
+    if sub is not None:
+        _dev(sub, torch.int32)
+        _dev(index_offsets, torch.int64, (ns + 1,))
+    if nreq > 0 and sub is not None:  # nothing reads outside comp or sub or writes outside out: one host read
+        ok = (req_count >= 0).all() & (out_begin >= 0).all() & (req_count <= out.numel()).all()
+        ok &= (out_begin <= out.numel() - req_count).all()
+        if ns > 0:
+            ok &= (comp_offsets.min() >= 0) & (comp_offsets.max() <= comp.numel())
+            ok &= (index_offsets.min() >= 0) & (index_offsets.max() <= sub.numel())
+        if not bool(ok.item()):
+            raise ValueError("offsets must lie inside their buffers, and out_begin + req_count inside out")
+    status = torch.zeros(nreq, dtype=torch.int32, device=offsets.device)
+    _check(load().huff_batch_decode_ranges(ctx.h, _p(comp), _p(comp_offsets), _p(bits), _p(codes), _p(sub),
+                                           _p(index_offsets if sub is not None else None), _p(offsets), _p(status_in),
+                                           ns, _p(req_stream), _p(req_first), _p(req_count), _p(out_begin), nreq,
+                                           _p(out), _p(status)))
     return status
 
 
@@ -408,3 +469,52 @@ def decompress_batch(ctx, c: BatchCompressed):
     status = batch_decode(ctx, c.comp, c.comp_offsets, c.bits, c.trees.codes, c.sub, c.index_offsets, c.offsets,
                           c.status, out)
     return out, status
+
+
+def _req(x, dtype, dev) -> torch.Tensor:
+    return torch.as_tensor(x, dtype=dtype, device=dev).reshape(-1).contiguous()
+
+
+def decompress_ranges(ctx, c: BatchCompressed, req_stream, req_first, req_count):
+    """(letters u8, out_offsets [R + 1] int64, status [R] int32): the letters
+    [req_first[r], req_first[r] + req_count[r]) of stream req_stream[r] of c,
+    tightly concatenated in request order (out_offsets is the scan of the
+    counts), through the restart index: one launch that decodes only the
+    64-letter blocks the ranges touch, and two host reads. A request whose
+    status is not 0 (include/huffgpu.h, huff_batch_decode_ranges) keeps its
+    slot, zero-filled. c may come from compress_batch or from from_bytes."""
+    dev = c.comp.device
+    req_stream = _req(req_stream, torch.int32, dev)
+    req_first = _req(req_first, torch.int64, dev)
+    req_count = _req(req_count, torch.int64, dev)
+    nreq = req_stream.numel()
+    assert req_first.numel() == nreq and req_count.numel() == nreq
+    out_offsets = _scan(req_count)
+    if nreq == 0:
+        return (torch.zeros(0, dtype=torch.uint8, device=dev), out_offsets,
+                torch.zeros(0, dtype=torch.int32, device=dev))
+    lowest, total = torch.stack((req_count.min(), out_offsets[-1])).tolist()
+    if lowest < 0:
+        raise ValueError("req_count must not be negative")
+    out = torch.zeros(total, dtype=torch.uint8, device=dev)
+    status = batch_decode_ranges(ctx, c.comp, c.comp_offsets, c.bits, c.trees.codes, c.sub, c.index_offsets, c.offsets,
+                                 c.status, req_stream, req_first, req_count, out_offsets[:-1].contiguous(), out)
+    bad = status != 0
+    if bool(bad.any().item()):  # a corrupt request may have written some of its bytes
+        out[torch.repeat_interleave(bad, req_count, output_size=total)] = 0
+    return out, out_offsets, status
+
+
+def decompress_streams(ctx, c: BatchCompressed, stream_ids):
+    """decompress_ranges of the whole streams stream_ids[r] (first 0, count
+    n_s): (letters, out_offsets [R + 1], status [R]). An id outside the batch
+    owns no letters and gets E_INVALID_ARG."""
+    dev = c.comp.device
+    ids = _req(stream_ids, torch.int64, dev)
+    ns = c.offsets.numel() - 1
+    counts = torch.clamp(c.offsets[1:] - c.offsets[:-1], min=0)
+    valid = (ids >= 0) & (ids < ns)
+    req_count = torch.where(valid, counts[ids.clamp(0, max(ns - 1, 0))], torch.zeros_like(ids)) if ns > 0 \
+        else torch.zeros_like(ids)
+    req_stream = torch.where(valid, ids, torch.full_like(ids, ns)).to(torch.int32)
+    return decompress_ranges(ctx, c, req_stream, torch.zeros_like(ids), req_count)

@@ -388,6 +388,59 @@ int huff_batch_decode(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_co
                       const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out,
                       uint32_t* d_status);
 
+/* Letter ranges of chosen streams of a batch through the restart index, in
+ * one launch (device pointers, synchronous on the context's stream; DESIGN.md
+ * §12, "Letter ranges through the index"). The batch is described as for
+ * huff_batch_decode; d_sub is required (a stream that came without an index
+ * gets one from huff_batch_count / huff_batch_index).
+ *  huff_batch_decode_ranges: request r asks for the letters [f, f + m) of
+ *                     stream s = d_req_stream[r], f = d_req_first[r], m =
+ *                     d_req_count[r], and gets them at d_out +
+ *                     d_req_out_begin[r]. Only the 64-letter blocks f / 64 ..
+ *                     (f + m - 1) / 64 of the stream are decoded, each one
+ *                     whole and under huff_batch_decode's rule: block j starts
+ *                     at d_sub[d_index_offsets[s] + j] and must end exactly at
+ *                     the next entry (the stream's last block: at d_bits[s]).
+ *                     d_req_status[r], the first that applies:
+ *                      HUFF_E_INVALID_ARG  s >= nstreams, or f + m overflows or
+ *                                          exceeds n_s; nothing written.
+ *                      d_status_in[s]      if that is not HUFF_OK; nothing
+ *                                          written.
+ *                      HUFF_OK             m == 0: nothing written, nothing
+ *                                          decoded.
+ *                      HUFF_E_CORRUPT      the stream's own numbers disagree
+ *                                          (d_bits[s] >= 2^32, its bytes are
+ *                                          not ceil(d_bits[s] / 8), n_s >
+ *                                          d_bits[s], its index entries are
+ *                                          not ceil(n_s / 64)); nothing
+ *                                          written.
+ *                      HUFF_E_CORRUPT      a touched block has a window that
+ *                                          matches no code, a code crossing
+ *                                          its end, an end elsewhere, a first
+ *                                          entry other than 0, or an end past
+ *                                          d_bits[s]; only bytes among the
+ *                                          request's own m output bytes may
+ *                                          have been written.
+ *                      HUFF_OK             otherwise: exactly its m bytes.
+ *                     A request reads only its stream's compressed bytes and
+ *                     the index entries of the blocks it touches (and the one
+ *                     after them), and writes only d_out[d_req_out_begin[r],
+ *                     d_req_out_begin[r] + m). Requests are independent, also
+ *                     on one stream: a bad entry j of the index makes exactly
+ *                     the requests that touch block j - 1 or block j corrupt.
+ *                     Output ranges of different requests that overlap are
+ *                     the caller's business: each such byte gets one of the
+ *                     requests' letters. nreq == 0: HUFF_OK, no launch. d_sub
+ *                     NULL, or any other required pointer NULL, with nreq > 0:
+ *                     HUFF_E_INVALID_ARG. */
+int huff_batch_decode_ranges(huff_ctx* ctx, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                             const uint64_t* d_bits, const uint64_t* d_codes, const uint32_t* d_sub,
+                             const uint64_t* d_index_offsets, const uint64_t* d_offsets,
+                             const uint32_t* d_status_in, uint32_t nstreams,
+                             const uint32_t* d_req_stream, const uint64_t* d_req_first,
+                             const uint64_t* d_req_count, const uint64_t* d_req_out_begin, uint32_t nreq,
+                             uint8_t* d_out, uint32_t* d_req_status);
+
 /* The batch as containers and back (device pointers unless named h_,
  * synchronous, on the context's stream). Stream s's blob is
  * CompressData::to_bytes of it alone (comp.rs:279-300):

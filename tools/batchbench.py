@@ -21,6 +21,13 @@ job, of the unchanged serial index-free decode (huff_batch_decode without an
 index, given the true letter counts) that count + index + indexed decode
 replace; the wall time of to_bytes and of from_bytes + decompress_batch; and
 k_hist_batch, which reads the same bytes once, beside them.
+
+--ranges adds the random-access decode (huff_batch_decode_ranges) on the same
+two inputs: kernel times of a sparse case (1,000 requests of 256 letters at
+random places in 1,000 distinct random streams), a medium case (4,096 letters at
+a random place in every stream) and a dense case (every stream whole), and, in
+the same job, of the full indexed huff_batch_decode, the only other route to
+any of those letters. Every case's output is compared with the slices first.
 """
 import argparse
 import json
@@ -184,6 +191,64 @@ def container(ctx, kind, S, L, iters):
     return res
 
 
+def ranges(ctx, kind, S, L, iters):
+    """letter ranges of S streams of L bytes of `kind` through the index, and
+    the full indexed decode of the batch beside them"""
+    from huff_coding import device
+
+    n = S * L
+    data = torch.empty(n, dtype=torch.uint8, device="cuda")
+    device.generate(ctx, kind, 11, data.data_ptr(), n, cdf=device.zipf_cdf(1.2) if kind == "zipf" else None)
+    offs = torch.arange(0, S + 1, device="cuda", dtype=torch.int64) * L
+    c = batch.compress_batch(ctx, data, offs)
+    full = torch.empty(n, dtype=torch.uint8, device="cuda")
+    st = batch.batch_decode(ctx, c.comp, c.comp_offsets, c.bits, c.trees.codes, c.sub, c.index_offsets, offs, c.status, full)
+    torch.cuda.synchronize()
+    assert int((c.status != 0).sum()) == 0 and int((st != 0).sum()) == 0 and torch.equal(full, data)
+    rng = np.random.default_rng(23)
+    ns, ls, lm = min(1000, S), min(256, L), min(4096, L)
+    cases = {
+        "sparse": (rng.permutation(S)[:ns], rng.integers(0, L - ls + 1, ns), np.full(ns, ls)),
+        "medium": (np.arange(S), rng.integers(0, L - lm + 1, S), np.full(S, lm)),
+        "dense": (np.arange(S), np.zeros(S, np.int64), np.full(S, L)),
+    }
+    res = {"kind": kind, "comp_ratio": round(c.comp.numel() / n, 4), "lib": os.environ.get("HUFF_LIB_AB", "default")}
+    ctx.set_timing(True)
+    ctx.reset_timing()
+    for _ in range(iters):
+        batch.batch_decode(ctx, c.comp, c.comp_offsets, c.bits, c.trees.codes, c.sub, c.index_offsets, offs, c.status, full)
+    ms, cnt = ctx.kernel_time("batch_decode")
+    res["batch_decode_ms"] = round(ms / cnt, 4)
+    for name, (rs, rf, rc) in cases.items():
+        rs_t = torch.from_numpy(rs.astype(np.int32)).cuda()
+        rf_t = torch.from_numpy(rf.astype(np.int64)).cuda()
+        rc_t = torch.from_numpy(rc.astype(np.int64)).cuda()
+        begins = torch.cumsum(rc_t, 0) - rc_t
+        out = torch.zeros(int(rc.sum()), dtype=torch.uint8, device="cuda")
+
+        def run():
+            return batch.batch_decode_ranges(ctx, c.comp, c.comp_offsets, c.bits, c.trees.codes, c.sub, c.index_offsets,
+                                             offs, c.status, rs_t, rf_t, rc_t, begins, out)
+
+        st = run()  # warm-up, and the check that what is timed is right
+        torch.cuda.synchronize()
+        assert int((st != 0).sum()) == 0
+        src = (rs_t.to(torch.int64) * L + rf_t)[:, None] + torch.arange(int(rc[0]), device="cuda")[None, :]
+        assert torch.equal(out, data[src.reshape(-1)]), name
+        del src
+        ctx.reset_timing()
+        for _ in range(iters):
+            run()
+        torch.cuda.synchronize()
+        ms, cnt = ctx.kernel_time("batch_decode_ranges")
+        res[name + "_requests"] = int(rs.size)
+        res[name + "_letters"] = int(rc.sum())
+        res[name + "_ms"] = round(ms / cnt, 4)
+        res[name + "_over_full_decode"] = round(ms / cnt / res["batch_decode_ms"], 4)
+    ctx.set_timing(False)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=10000)
@@ -192,6 +257,7 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=500, help="streams built on the host for comparison")
     ap.add_argument("--codec", action="store_true", help="also the batched codec and the per-stream loop")
     ap.add_argument("--container", action="store_true", help="also the batch's containers and the parallel count")
+    ap.add_argument("--ranges", action="store_true", help="also letter ranges through the index (random access)")
     ap.add_argument("--loop-sample", type=int, default=200, help="streams of the per-stream loop")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -237,6 +303,9 @@ def main():
     if args.container:
         ctx.set_timing(False)
         res["container"] = [container(ctx, kind, S, L, args.iters) for kind in ("uniform", "zipf")]
+    if args.ranges:
+        ctx.set_timing(False)
+        res["ranges"] = [ranges(ctx, kind, S, L, args.iters) for kind in ("uniform", "zipf")]
     print(json.dumps(res), flush=True)
 
 
