@@ -835,9 +835,7 @@ int huff_batch_unwrap(huff_ctx* ctx, const uint8_t* d_blobs, const uint64_t* d_p
 }
 
 size_t huff_batch_seg_entries(size_t total_comp_bytes, uint32_t nstreams) {
-#ifndef HUFF_BATCH_SEG_BITS_AB
     static_assert(HUFF_BATCH_SEG_BITS == huff::kBatchSegBits, "the header states the kernels' segment");
-#endif
     return static_cast<size_t>(huff::batch_seg_entries(total_comp_bytes, nstreams));
 }
 

@@ -31,29 +31,19 @@
 //                  kIdx-letter block the range touches, each block decoded
 //                  whole under k_batch_decode's rule and only the wanted
 //                  letters stored.
-#include "batch_lut.hpp"
+#include "batch_stream.hpp"
 #include "pack_emit.hpp"
 
 namespace huff::dev {
 
 namespace {
 
-// the measured knobs: lanes per stream's workgroup in pack
-// and decode, input bytes per lane of a short-code pack tile, index bits of
-// the decode table, a decode round's compressed bytes through LDS (1) or
-// read by each lane from global memory (0)
-#ifndef HUFF_BATCH_THREADS
-#define HUFF_BATCH_THREADS 256
-#endif
-#ifndef HUFF_BATCH_TILE
-#define HUFF_BATCH_TILE 16
-#endif
-#ifndef HUFF_BATCH_STAGE
-#define HUFF_BATCH_STAGE 1
-#endif
-constexpr uint32_t kBThreads = HUFF_BATCH_THREADS;
+// as measured: lanes per stream's workgroup in pack and
+// decode, and input bytes per lane of a short-code pack tile; a decode round's
+// compressed bytes always go through LDS where they fit
+constexpr uint32_t kBThreads = 256;
 constexpr uint32_t kBWaves = kBThreads / 64;
-constexpr int kBpN = HUFF_BATCH_TILE;  // long codes: 8
+constexpr int kBpN = 16;  // long codes: 8
 static_assert(kBpN == 8 || kBpN == 16, "whole dwords, at most one index entry per 4 lanes");
 static_assert(kBThreads % 64 == 0 && kBThreads >= 64 && kBThreads <= 1024, "whole waves");
 
@@ -358,7 +348,7 @@ __global__ __launch_bounds__(TH) void k_batch_decode(BatchDecodeArgs a) {
     __shared__ uint64_t tab[256];
     __shared__ uint8_t longl[256], coopl[256];
     __shared__ uint32_t nlong, ncoop, bad;
-    __shared__ __attribute__((aligned(16))) uint8_t cst[TH > 64 && HUFF_BATCH_STAGE ? kBdStageBytes : 16];
+    __shared__ __attribute__((aligned(16))) uint8_t cst[TH > 64 ? kBdStageBytes : 16];
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     const uint32_t st_in = a.status_in[s];
     if (st_in != kBatchOk) {
@@ -395,7 +385,7 @@ __global__ __launch_bounds__(TH) void k_batch_decode(BatchDecodeArgs a) {
             const uint32_t b_lo = sub[j0], b_hi = j0 + TH < nblk ? sub[j0 + TH] : end_all;
             uint32_t b0 = 0, span = 0;
             bool staged = false;
-            if (TH > 64 && HUFF_BATCH_STAGE && b_lo <= b_hi && b_hi <= end_all) {
+            if (TH > 64 && b_lo <= b_hi && b_hi <= end_all) {
                 b0 = (b_lo >> 3) & ~3u;
                 const uint32_t b1 = ((b_hi + 7) >> 3) + 8 < src.nbytes ? ((b_hi + 7) >> 3) + 8 : src.nbytes;
                 span = b1 - b0;
@@ -440,10 +430,7 @@ __global__ __launch_bounds__(TH) void k_batch_decode(BatchDecodeArgs a) {
 // The request reads sub[j0 .. j1 + 1] and the compressed bytes of its stream
 // only, and writes only its own m bytes. Lanes per request: measured at 64,
 // 128 and 256 ("Letter ranges through the index").
-#ifndef HUFF_BATCH_RANGE_THREADS
-#define HUFF_BATCH_RANGE_THREADS 128
-#endif
-constexpr uint32_t kBrThreads = HUFF_BATCH_RANGE_THREADS;
+constexpr uint32_t kBrThreads = 128;
 static_assert(kBrThreads % 64 == 0 && kBrThreads >= 64 && kBrThreads <= 1024, "whole waves");
 
 template <uint32_t TH>
@@ -453,7 +440,7 @@ __global__ __launch_bounds__(TH) void k_batch_decode_ranges(BatchRangesArgs a) {
     __shared__ uint64_t tab[256];
     __shared__ uint8_t longl[256], coopl[256];
     __shared__ uint32_t nlong, ncoop, bad;
-    __shared__ __attribute__((aligned(16))) uint8_t cst[HUFF_BATCH_STAGE ? kStage : 16];
+    __shared__ __attribute__((aligned(16))) uint8_t cst[kStage];
     const uint32_t r = blockIdx.x, t = threadIdx.x;
     // every early exit below is workgroup-uniform and comes before any barrier
     const uint32_t s = a.req_stream[r];
@@ -500,7 +487,7 @@ __global__ __launch_bounds__(TH) void k_batch_decode_ranges(BatchRangesArgs a) {
         const uint32_t b_lo = sub[j0], b_hi = je < nblk ? sub[je] : end_all;
         uint32_t b0 = 0, span = 0;
         bool staged = false;
-        if (HUFF_BATCH_STAGE && b_lo <= b_hi && b_hi <= end_all) {
+        if (b_lo <= b_hi && b_hi <= end_all) {
             b0 = (b_lo >> 3) & ~3u;
             const uint32_t b1 = ((b_hi + 7) >> 3) + 8 < src.nbytes ? ((b_hi + 7) >> 3) + 8 : src.nbytes;
             span = b1 - b0;

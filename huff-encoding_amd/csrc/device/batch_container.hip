@@ -40,7 +40,7 @@
 //  k_batch_index   one workgroup per stream: every lane walks its segments
 //                  again from their true entries and writes the bit offset of
 //                  each kIdx-th letter: huff_batch_pack's index.
-#include "batch_lut.hpp"
+#include "batch_stream.hpp"
 #include "bitreader.hpp"
 #include "host/batch_container.hpp"
 

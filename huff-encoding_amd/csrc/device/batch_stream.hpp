@@ -1,19 +1,17 @@
-// batch_lut.hpp — the per-stream decode table of the batch kernels
-// (k_batch_decode in batch_codec.hip; k_batch_count and k_batch_index in
-// batch_container.hip): a kBdLutBits-bit table of u16 (letter << 8 | len) in
-// LDS built from the stream's d_codes row, the list of the letters whose codes
-// are longer than the table's index, and the readers of a stream's compressed
-// bytes as big-endian words, from global memory or from a staged copy in LDS.
+// batch_stream.hpp — what a batch kernel needs to read one packed stream
+// (k_batch_decode and k_batch_decode_ranges in batch_codec.hip; k_batch_count
+// and k_batch_index in batch_container.hip): a kBdLutBits-bit table of u16
+// (letter << 8 | len) in LDS built from the stream's d_codes row, the list of
+// the letters whose codes are longer than the table's index, and the readers of
+// a stream's compressed bytes as big-endian words, from global memory or from a
+// staged copy in LDS.
 #pragma once
 
 #include "kernels.hpp"
 
 namespace huff::dev {
 
-#ifndef HUFF_BATCH_LUT_BITS
-#define HUFF_BATCH_LUT_BITS 12
-#endif
-constexpr uint32_t kBdLutBits = HUFF_BATCH_LUT_BITS;
+constexpr uint32_t kBdLutBits = 12;    // measured at 10, 11 and 12
 constexpr uint32_t kBdSlow = 0xFFu;    // len field of a table entry: the code is longer than the index
 constexpr uint32_t kBdCoop = 32;       // spans above this many entries are filled by the whole workgroup
 static_assert(kBdLutBits >= 8 && kBdLutBits <= kSsMaxBits, "u16 entries, whole 16-B clears");

@@ -16,11 +16,7 @@
 
 namespace huff {
 
-#ifdef HUFF_BATCH_SEG_BITS_AB  // a measurement build (tools/build_variant.sh), never the product's
-constexpr uint32_t kBatchSegBits = HUFF_BATCH_SEG_BITS_AB;
-#else
-constexpr uint32_t kBatchSegBits = 256;
-#endif
+constexpr uint32_t kBatchSegBits = 256;  // measured at 128, 256 and 512
 static_assert(kBatchSegBits % 8 == 0 && kBatchSegBits >= 64, "whole bytes; a 56-bit code rarely spans a segment");
 
 constexpr uint64_t batch_seg_offset(uint64_t comp_off_bytes, uint64_t stream) {

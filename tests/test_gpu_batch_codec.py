@@ -327,3 +327,58 @@ def test_batch_conveniences(H, O, ctx):
     out, st = batch.decompress_batch(ctx, c)
     assert st.cpu().tolist() == [batch.E_EMPTY_WEIGHTS] + [0] * (len(streams) - 1)
     assert out.cpu().numpy().tobytes() == ref.data[:-1].tobytes()
+
+
+def test_batch_decode_damaged_index(H, O, ctx):
+    """k_batch_decode<256> against a damaged restart index: stream 1 (40 000
+    letters: 625 blocks, three rounds of 256 lanes) gets one entry changed, or
+    the entry counts of streams 1 and 2 stop matching their letters. The
+    damaged stream answers E_CORRUPT, its neighbours decode to exactly their
+    letters, and nothing is written outside the output."""
+    import torch
+
+    from huff_coding import batch
+
+    rng = np.random.default_rng(31)
+    streams = [rng.integers(0, 7, n).astype(np.uint8) for n in (200, 40_000, 130, 5_000)]
+    offs = np.zeros(len(streams) + 1, np.int64)
+    offs[1:] = np.cumsum([x.size for x in streams])
+    c = batch.compress_batch(ctx, torch.from_numpy(np.concatenate(streams)).cuda(), torch.from_numpy(offs).cuda())
+    assert (c.status == 0).all()
+    ioff, bits = c.index_offsets.cpu().numpy(), c.bits.cpu().numpy()
+    assert ioff.tolist() == [0, 4, 629, 632, 711]
+    i1 = int(ioff[1])
+
+    def one_bit_off(sub, io):
+        sub[i1 + 256] += 1  # a round's first entry
+
+    def out_of_order(sub, io):
+        # sub is an int32 tensor that the kernels read as u32: -16 is 0xFFFFFFF0. The round's
+        # entries are then not in order, so it is not staged
+        sub[i1 + 256] = -16
+
+    def first_not_zero(sub, io):
+        sub[i1] = 1
+
+    def past_the_end(sub, io):
+        sub[i1 + 624] = int(bits[1]) + 8
+
+    def counts_disagree(sub, io):
+        io[2] -= 1  # streams 1 and 2
+
+    def nothing(sub, io):
+        pass
+
+    C = batch.E_CORRUPT
+    cases = [(one_bit_off, [0, C, 0, 0]), (out_of_order, [0, C, 0, 0]), (first_not_zero, [0, C, 0, 0]),
+             (past_the_end, [0, C, 0, 0]), (counts_disagree, [0, C, C, 0]), (nothing, [0, 0, 0, 0])]
+    for damage, want in cases:
+        sub, io = c.sub.clone(), c.index_offsets.clone()
+        damage(sub, io)
+        p = dict(out=c.comp, coff=c.comp_offsets, bits=c.bits, codes=c.trees.codes, sub=sub, ioff=io,
+                 offs=c.offsets, status=c.status)
+        out, st = _decode(torch, batch, ctx, p, indexed=True)  # 0xEE-filled, exactly sized, guards checked
+        assert st.tolist() == want, damage.__name__
+        for s, x in enumerate(streams):
+            if want[s] == 0:
+                assert np.array_equal(out[offs[s]: offs[s + 1]], x), (damage.__name__, s)
