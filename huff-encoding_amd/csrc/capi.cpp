@@ -59,6 +59,10 @@ uint64_t huff_diag_decode_build_launches(uint32_t i) { return huff::dev::decode_
 uint32_t huff_diag_decode_index_forms(void) { return huff::dev::decode_fixed_index_forms(); }
 const char* huff_diag_decode_index_form_name(uint32_t i) { return huff::dev::decode_fixed_index_form_name(i); }
 uint64_t huff_diag_decode_index_form_launches(uint32_t i) { return huff::dev::decode_fixed_index_form_launches(i); }
+// ... and the range kernel's launches
+uint32_t huff_diag_range_index_forms(void) { return huff::dev::decode_ranges_index_forms(); }
+const char* huff_diag_range_index_form_name(uint32_t i) { return huff::dev::decode_ranges_index_form_name(i); }
+uint64_t huff_diag_range_index_form_launches(uint32_t i) { return huff::dev::decode_ranges_index_form_launches(i); }
 
 // --------------------------------------------------------------------------
 int huff_ctx_create(int device, huff_ctx** out) {
@@ -531,6 +535,23 @@ int huff_enc_decode(huff_enc* e, const huff_tree* t, const uint8_t* d_comp, uint
         const uint64_t bytes = ((e->bit_base & 7) + e->total_bits + 7) / 8;
         return e->decode(t, d_comp, bytes, d_out);
     });
+}
+
+int huff_enc_decode_ranges(huff_enc* e, const huff_tree* t, const uint8_t* d_comp, const uint64_t* first,
+                           const uint64_t* count, const uint64_t* out_begin, uint32_t nreq, uint8_t* d_out,
+                           size_t out_cap, uint32_t* status) {
+    if (!e || !t || !d_comp || (nreq && (!first || !count || !out_begin || !status)) || (!d_out && out_cap))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        const uint64_t bytes = ((e->bit_base & 7) + e->total_bits + 7) / 8;
+        return e->decode_ranges(t, d_comp, bytes, first, count, out_begin, nreq, d_out, out_cap, status);
+    });
+}
+
+int huff_decompress_range(huff_ctx* ctx, const huff_compress_data* cd, uint64_t first, uint64_t count, uint8_t* out,
+                          size_t cap) {
+    if (!ctx || !cd || (!out && cap)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::decompress_range_host(ctx, cd, first, count, out, cap); });
 }
 
 int huff_dev_decompress(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, size_t comp_bytes,

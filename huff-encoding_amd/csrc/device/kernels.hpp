@@ -627,6 +627,39 @@ uint64_t decode_fixed_build_launches(uint32_t i);
 uint32_t decode_fixed_index_forms();
 const char* decode_fixed_index_form_name(uint32_t i);
 uint64_t decode_fixed_index_form_launches(uint32_t i);
+// Letter ranges of one indexed stream (decode_ranges.hip): request r is the
+// letters [first, first + count) stored at out + out_begin; its pieces
+// (host/range_plan.hpp) are the launch's pieces [piece0, next request's
+// piece0). The requests are sorted by piece0 (each has at least one piece) and
+// were checked on the host: the range lies inside [0, n].
+struct RangeReq {
+    uint64_t first, count, out_begin, piece0;
+    uint32_t index;  // the caller's request: its status word
+    uint32_t pad;
+};
+struct RangesArgs {
+    const uint8_t* comp;          // 4-B aligned
+    uint64_t comp_bytes;
+    const uint32_t* lut;          // DecodeArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint64_t* chunk_start;  // [nchunks + 1]
+    const uint32_t* sub_bit;      // with chunk_start, unless:
+    const uint16_t* sub16;        // the compact index, with task_base
+    const uint64_t* task_base;
+    uint32_t nchunks;
+    uint64_t n;
+    const RangeReq* req;
+    uint32_t nreq;                // >= 1
+    uint64_t npieces;
+    uint8_t* out;
+    uint32_t* status;             // zeroed; atomicMax of kBatchCorrupt
+};
+hipError_t launch_decode_ranges(const RangesArgs& a, hipStream_t s);
+// diagnostics (huffgpu.h huff_diag_range_*): the forms the range kernel's
+// launches read the index in, with process-wide launch counts
+uint32_t decode_ranges_index_forms();
+const char* decode_ranges_index_form_name(uint32_t i);
+uint64_t decode_ranges_index_form_launches(uint32_t i);
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

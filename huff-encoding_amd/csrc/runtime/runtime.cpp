@@ -1,6 +1,8 @@
 // runtime.cpp — context, encode job and host-pointer pipelines.
 #include "runtime.hpp"
 
+#include "../host/range_plan.hpp"
+
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -787,6 +789,71 @@ huff::Status huff_enc::decode(const huff_tree* t, const uint8_t* d_comp, uint64_
     return huff::Status::ok();
 }
 
+static_assert(huff::kRangeBlock == huff::dev::kIdx, "host/range_plan.hpp mirrors dev::kIdx");
+
+huff::Status huff_enc::decode_ranges(const huff_tree* t, const uint8_t* d_comp, uint64_t comp_bytes,
+                                     const uint64_t* first, const uint64_t* count, const uint64_t* out_begin,
+                                     uint32_t nreq, uint8_t* d_out, size_t out_cap, uint32_t* status) {
+    if (!packed) return huff::Status::err(HUFF_E_STATE, "no restart index: pack (or upload an index) first");
+    if (!codes_match(t))
+        return huff::Status::err(HUFF_E_STATE, "decode tree differs from the tree the stream was packed (or its index "
+                                               "uploaded) with");
+    if (reinterpret_cast<uintptr_t>(d_comp) & 3)
+        return huff::Status::err(HUFF_E_INVALID_ARG, "compressed stream must be 4-byte aligned");
+    const huff::DecTables* dt = nullptr;
+    HUFF_TRY(t->dec_tables(&dt));
+    if (dt->maxdepth > huff::dev::kLongMaxLen)
+        return huff::Status::err(HUFF_E_CODE_TOO_LONG, "letter ranges need codes of at most 57 bits: decode the "
+                                                       "stream whole (huff_enc_decode)");
+    // the requests that pass both range checks and have letters, in the
+    // caller's order, each with its first piece of the launch
+    std::vector<huff::dev::RangeReq> req;
+    uint64_t npieces = 0;
+    for (uint32_t r = 0; r < nreq; ++r) {
+        const bool ok = huff::range_inside(first[r], count[r], n) && huff::range_inside(out_begin[r], count[r], out_cap);
+        status[r] = ok ? HUFF_OK : HUFF_E_INVALID_ARG;
+        if (!ok || count[r] == 0) continue;
+        req.push_back({first[r], count[r], out_begin[r], npieces, r, 0});
+        npieces += huff::range_pieces(first[r], count[r]);
+    }
+    if (req.empty()) return huff::Status::ok();
+    HUFF_TRY(ctx->activate());
+    HUFF_TRY(ctx->upload_dec_tables(t, &dt));
+    HUFF_TRY(ensure_index());  // a byte-map pack's index, still pending; a compact index stays compact
+    HUFF_TRY(range_req.ensure(req.size() * sizeof(huff::dev::RangeReq)));
+    HUFF_TRY(range_status.ensure(static_cast<size_t>(nreq) * 4));
+    HIP_TRY(hipMemcpyAsync(range_req.p, req.data(), req.size() * sizeof(huff::dev::RangeReq), hipMemcpyHostToDevice,
+                           ctx->stream));
+    HIP_TRY(hipMemsetAsync(range_status.p, 0, static_cast<size_t>(nreq) * 4, ctx->stream));
+    huff::dev::RangesArgs a{};
+    a.comp = d_comp;
+    a.comp_bytes = comp_bytes;
+    a.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
+    a.lut_bits = dt->bits;
+    a.chunk_start = static_cast<const uint64_t*>(chunk_start.p);
+    if (compact_index) {
+        a.sub16 = static_cast<const uint16_t*>(sub16.p);
+        a.task_base = static_cast<const uint64_t*>(task_base.p);
+    } else {
+        a.sub_bit = static_cast<const uint32_t*>(sub_bit.p);
+    }
+    a.nchunks = nchunks;
+    a.n = n;
+    a.req = static_cast<const huff::dev::RangeReq*>(range_req.p);
+    a.nreq = static_cast<uint32_t>(req.size());
+    a.npieces = npieces;
+    a.out = d_out;
+    a.status = static_cast<uint32_t*>(range_status.p);
+    HUFF_TRY(ctx->timed("decode_ranges", [&] { return huff::dev::launch_decode_ranges(a, ctx->stream); }));
+    HIP_TRY(hipEventRecord(ctx->lut_free, ctx->stream));
+    std::vector<uint32_t> st(nreq);
+    HIP_TRY(hipMemcpyAsync(st.data(), range_status.p, static_cast<size_t>(nreq) * 4, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HUFF_TRY(ctx->sync());  // also: req has left the host
+    for (const auto& q : req) status[q.index] = st[q.index];
+    return huff::Status::ok();
+}
+
 huff::Status huff_enc::download_index(huff_index_host& idx) {
     HUFF_TRY(ensure_index());
     HUFF_TRY(expand_index());  // the host index (CompressData) keeps chunk_start + sub_bit
@@ -957,6 +1024,47 @@ Status decompress_host(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out
     HUFF_TRY(e.decode(cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(),
                       static_cast<uint8_t*>(ctx->d_out.p)));
     HIP_TRY(hipMemcpyAsync(out, ctx->d_out.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    return ctx->sync();
+}
+
+Status decompress_range_host(huff_ctx* ctx, const huff_compress_data* cd, uint64_t first, uint64_t count,
+                             uint8_t* out, size_t cap) {
+    const DecTables* dt = nullptr;
+    HUFF_TRY(cd->tree->dec_tables(&dt));
+    if (!cd->index || dt->maxdepth > dev::kLongMaxLen) {  // the slow route: everything, then the slice
+        std::vector<uint8_t> all;
+        if (!cd->index) {
+            const uint64_t valid = static_cast<uint64_t>(cd->comp.size()) * 8 - cd->padding;
+            HUFF_TRY(decode_indexless_host(ctx, cd->comp.data(), cd->comp.size(), valid, cd->tree, all));
+        } else {
+            all.resize(cd->index->n);
+            size_t len = 0;
+            HUFF_TRY(decompress_host(ctx, cd, all.data(), all.size(), &len));
+        }
+        if (!range_inside(first, count, all.size()))
+            return Status::err(HUFF_E_INVALID_ARG, "letter range outside the stream");
+        if (cap < count) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+        if (count) std::memcpy(out, all.data() + first, count);
+        return Status::ok();
+    }
+    const uint64_t n = cd->index->n;
+    if (!range_inside(first, count, n)) return Status::err(HUFF_E_INVALID_ARG, "letter range outside the stream");
+    if (cap < count) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+    if (count == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    HUFF_TRY(ctx->d_in.ensure(cd->comp.size() + 16));
+    HIP_TRY(hipMemcpyAsync(ctx->d_in.p, cd->comp.data(), cd->comp.size(), hipMemcpyHostToDevice, ctx->stream));
+    HUFF_TRY(ctx->d_out.ensure(count + 16));
+    huff_enc e;
+    // the job's input pointer is unused by decode; give it the output staging (aligned)
+    HUFF_TRY(e.init(ctx, static_cast<const uint8_t*>(ctx->d_out.p), n));
+    HUFF_TRY(e.upload_index(*cd->index));
+    const uint64_t zero = 0;
+    uint32_t st = 0;
+    HUFF_TRY(e.decode_ranges(cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(), &first, &count,
+                             &zero, 1, static_cast<uint8_t*>(ctx->d_out.p), count, &st));
+    if (st != HUFF_OK) return Status::err(static_cast<int>(st), "the stream does not decode along its restart index");
+    HIP_TRY(hipMemcpyAsync(out, ctx->d_out.p, count, hipMemcpyDeviceToHost, ctx->stream));
     return ctx->sync();
 }
 

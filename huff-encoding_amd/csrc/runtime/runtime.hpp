@@ -250,6 +250,12 @@ struct huff_enc {
     huff::Status pack(const huff_tree* t, uint64_t bit_base, const uint8_t* prev_tail, size_t prev_tail_len,
                       uint8_t* d_out, size_t out_cap, uint64_t* total);
     huff::Status decode(const huff_tree* t, const uint8_t* d_comp, uint64_t comp_bytes, uint8_t* d_out);
+    // letter ranges through the restart index as it stands (huff_enc_decode_ranges,
+    // decode_ranges.hip); first, count, out_begin and status are host arrays
+    DevBuf range_req, range_status;
+    huff::Status decode_ranges(const huff_tree* t, const uint8_t* d_comp, uint64_t comp_bytes, const uint64_t* first,
+                               const uint64_t* count, const uint64_t* out_begin, uint32_t nreq, uint8_t* d_out,
+                               size_t out_cap, uint32_t* status);
     huff::Status download_index(huff_index_host& idx);
     huff::Status upload_index(const huff_index_host& idx);
 };
@@ -261,6 +267,10 @@ Status weights_threaded_from_host(huff_ctx* ctx, const uint8_t* bytes, size_t n,
                                   ByteWeights& out);
 Status compress_host(huff_ctx* ctx, const uint8_t* bytes, size_t n, const huff_tree* t, huff_compress_data** out);
 Status decompress_host(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
+// the letters [first, first + count) of cd: through the range kernel when cd
+// has an index and a tree of at most kLongMaxLen bits, else decoded whole and sliced
+Status decompress_range_host(huff_ctx* ctx, const huff_compress_data* cd, uint64_t first, uint64_t count,
+                             uint8_t* out, size_t cap);
 Status file_compress(huff_ctx* ctx, const char* src, const char* dst, size_t block_size);
 Status file_decompress(huff_ctx* ctx, const char* src, const char* dst, size_t block_size);
 Status parse_block_size(const char* s, size_t* out);

@@ -32,7 +32,7 @@ from ._lib import load
 
 __all__ = [
     "ByteWeights", "HuffTree", "HuffBranch", "HuffLeaf", "CompressData", "compress", "compress_with_tree", "decompress",
-    "read_compress_write", "read_decompress_write", "parse_block_size", "Context", "EncodeJob",
+    "decompress_range", "read_compress_write", "read_decompress_write", "parse_block_size", "Context", "EncodeJob",
     "HuffError", "HuffPanic", "CompressError", "FromBinError", "CompressedDataFromBytesError",
 ]
 
@@ -485,6 +485,22 @@ def decompress(comp_data: CompressData, ctx: Optional[Context] = None) -> bytes:
     _check(load().huff_decompress(ctx.h, comp_data.h, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
                                   C.byref(n)))
     return out[: n.value].tobytes()
+
+
+def decompress_range(comp_data: CompressData, first: int, count: int, ctx: Optional[Context] = None) -> bytes:
+    """decompress(comp_data)[first:first + count] without decoding the rest
+    (huff_decompress_range): data from compress / compress_with_tree carries a
+    restart index and decodes only the 64-letter blocks the range touches; data
+    from try_from_bytes, or with codes longer than 57 bits, is decoded whole and
+    sliced (the slow route). A range outside the stream raises
+    HuffError(INVALID_ARG)."""
+    ctx = ctx or default_context()
+    if first < 0 or first >= 1 << 64 or count < 0 or count >= 1 << 48:  # a stream holds fewer than 2^48 letters
+        raise HuffError(_lib.E_INVALID_ARG, "letter range outside the stream")
+    out = np.empty(max(count, 1), np.uint8)
+    _check(load().huff_decompress_range(ctx.h, comp_data.h, first, count, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        count))
+    return out[:count].tobytes()
 
 
 # --------------------------------------------------------------------------

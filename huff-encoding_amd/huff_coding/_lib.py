@@ -91,6 +91,7 @@ SIGNATURES = [
     ("huff_compress_with_tree", i, [vp, vp, sz, vp, C.POINTER(vp)]),
     ("huff_compress_bytes", i, [vp, vp, sz, C.POINTER(vp)]),
     ("huff_decompress", i, [vp, vp, u8p, sz, szp]),
+    ("huff_decompress_range", i, [vp, vp, C.c_uint64, C.c_uint64, u8p, sz]),
     ("huff_enc_create", i, [vp, vp, sz, C.POINTER(vp)]),
     ("huff_enc_free", None, [vp]),
     ("huff_enc_hist", i, [vp, vp]),
@@ -101,6 +102,7 @@ SIGNATURES = [
     ("huff_enc_pack_shards", i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, C.POINTER(vp), u64p, u64p]),
     ("huff_enc_compress", i, [vp, vp, sz, C.POINTER(vp), u64p]),
     ("huff_enc_decode", i, [vp, vp, vp, vp]),
+    ("huff_enc_decode_ranges", i, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp]),
     ("huff_dev_decompress", i, [vp, vp, vp, sz, C.c_uint8, vp, sz, szp]),
     ("huff_batch_hist", i, [vp, vp, vp, C.c_uint32, vp]),
     ("huff_batch_trees", i, [vp, vp, C.c_uint32, vp, sz, vp, vp, vp, vp]),
@@ -137,6 +139,9 @@ SIGNATURES = [
     ("huff_diag_decode_index_forms", C.c_uint32, []),
     ("huff_diag_decode_index_form_name", C.c_char_p, [C.c_uint32]),
     ("huff_diag_decode_index_form_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_diag_range_index_forms", C.c_uint32, []),
+    ("huff_diag_range_index_form_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_range_index_form_launches", C.c_uint64, [C.c_uint32]),
     # include/huffgpu_wide.h
     ("huff_wtree_from_weights", i, [C.c_uint32, vp, vp, sz, C.POINTER(vp)]),
     ("huff_wtree_clone", i, [vp, C.POINTER(vp)]),
@@ -209,6 +214,13 @@ def decode_index_form_launches() -> dict:
     L = load()
     return {L.huff_diag_decode_index_form_name(k).decode(): L.huff_diag_decode_index_form_launches(k)
             for k in range(L.huff_diag_decode_index_forms())}
+
+
+def range_index_form_launches() -> dict:
+    """{index form: range-kernel launches so far} (huff_diag_range_index_form_*)"""
+    L = load()
+    return {L.huff_diag_range_index_form_name(k).decode(): L.huff_diag_range_index_form_launches(k)
+            for k in range(L.huff_diag_range_index_forms())}
 
 
 def wide_build_launches() -> dict:

@@ -125,6 +125,34 @@ class EncodeJob:
         """block-parallel decode of this job's pack output via its restart index"""
         _check(load().huff_enc_decode(self.h, tree.h, C.c_void_p(d_comp), C.c_void_p(d_out)))
 
+    def decode_ranges(self, tree, d_comp: int, first, count, d_out: int, out_cap: int, out_begin=None) -> np.ndarray:
+        """random access into this job's pack output (huff_enc_decode_ranges):
+        the letters [first[r], first[r] + count[r]) land at d_out +
+        out_begin[r]; only the 64-letter blocks they touch are decoded.
+        out_begin=None lays the requests out tightly in request order. Returns
+        the requests' statuses (uint32: 0, E_INVALID_ARG for a range outside
+        the job or a slot outside out_cap, E_CORRUPT)."""
+        f = np.ascontiguousarray(first, np.uint64).reshape(-1)
+        c = np.ascontiguousarray(count, np.uint64).reshape(-1)
+        if f.size != c.size:
+            raise ValueError("first and count differ in length")
+        if out_begin is None:
+            ob = np.zeros(f.size, np.uint64)
+            if f.size:  # Python sums: a count near 2^64 must not wrap a position back into the buffer
+                pos = 0
+                for r, m in enumerate(c.tolist()):
+                    ob[r] = min(pos, 0xFFFFFFFFFFFFFFFF)
+                    pos += m
+        else:
+            ob = np.ascontiguousarray(out_begin, np.uint64).reshape(-1)
+            if ob.size != f.size:
+                raise ValueError("first and out_begin differ in length")
+        st = np.zeros(f.size, np.uint32)
+        _check(load().huff_enc_decode_ranges(self.h, tree.h, C.c_void_p(d_comp), f.ctypes.data, c.ctypes.data,
+                                             ob.ctypes.data, f.size, C.c_void_p(d_out) if d_out else None, out_cap,
+                                             st.ctypes.data))
+        return st
+
 
 def decompress_dev(ctx, tree, d_comp: int, comp_bytes: int, padding: int, d_out: int, out_cap: int) -> int:
     """comp.rs:487-519 on a device-resident stream with no restart index
