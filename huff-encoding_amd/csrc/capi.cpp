@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "runtime/indexless_rt.hpp"
 #include "runtime/runtime.hpp"
 
 #include "capi_util.hpp"

@@ -18,6 +18,8 @@
 
 #include <cstdint>
 
+#include "../host/indexless_plan.hpp"  // kLeadBits, kLeadBitsLong, kSampBits, kSampMax
+
 namespace huff::dev {
 
 // Kernel timing without marker packets. huff_ctx::timed() parks its event
@@ -226,23 +228,6 @@ struct IndexlessArgs {
     unsigned long long* wtot;
     uint64_t* stamps;             // timing builds (-DHUFF_STAMPS) only: per-wave phase stamps
 };
-// the staged speculative pass starts each lane up to kLeadBits before its
-// segment (indexless.hip k_spec_lds)
-#ifndef HUFF_LEAD_BITS
-#define HUFF_LEAD_BITS 128
-#endif
-constexpr uint32_t kLeadBits = HUFF_LEAD_BITS;
-// trees with codes longer than the walk table's index take longer to fall
-// onto the true path: twice the lead-in (wide letters, Zipf over 4,096:
-// W = 4 index-free 1.35 -> 1.27 ms, W = 2 2.01 -> 1.98; byte streams whose
-// codes all fit the table keep 128: 256 measured 1 % slower on text)
-constexpr uint32_t kLeadBitsLong = 2 * kLeadBits;
-// the speculative pass's sample spacing (indexless.hip); segments < 1024 bits
-#ifndef HUFF_SAMP_BITS
-#define HUFF_SAMP_BITS 96
-#endif
-constexpr uint32_t kSampBits = HUFF_SAMP_BITS;
-constexpr uint32_t kSampMax = 1023 / kSampBits;  // samples kept per segment (nsamp <= kSampMax)
 constexpr uint32_t kNoMerge = 0xFFFFFFFFu;
 constexpr int kFixRounds = 4;     // device-side fix-up rounds before the sequential fallback
 

@@ -31,6 +31,7 @@
 #include <string>
 #include <thread>
 
+#include "indexless_rt.hpp"
 #include "runtime.hpp"
 
 namespace huff {

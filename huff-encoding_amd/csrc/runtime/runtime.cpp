@@ -2,6 +2,7 @@
 #include "runtime.hpp"
 
 #include "../host/range_plan.hpp"
+#include "indexless_rt.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -97,7 +98,7 @@ namespace huff {
 //                           decoder wave several tasks at test sizes.
 //                           test_gpu_wide_builds
 //
-// Diagnostics stay beside the code they report on: HUFF_FIX_STATS (below),
+// Diagnostics stay beside the code they report on: HUFF_FIX_STATS (indexless_rt.cpp),
 // HUFF_TIME_FENCE / HUFF_TIME_MARKERS (huff_ctx::timed), HUFF_HOST_TRACE
 // (capi.cpp), HUFF_FILE_* (filepath.cpp).
 bool fixed8_disabled() {
@@ -149,9 +150,7 @@ uint64_t* stamp_region(int r) {
 }
 #endif
 
-// the k_decode_fixed part of DecodeArgs: the tables uploaded to d_lut, and
-// the stage and refill choices for a stream of `bits` bits holding n letters
-static void fill_fixed_decode(dev::DecodeArgs& a, const huff_ctx* ctx, const DecTables* dt, uint64_t bits, uint64_t n) {
+void fill_fixed_decode(dev::DecodeArgs& a, const huff_ctx* ctx, const DecTables* dt, uint64_t bits, uint64_t n) {
     a.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
     a.lut_bits = dt->bits;
     a.lut_words = static_cast<uint32_t>(dt->lut.size());
@@ -314,6 +313,14 @@ huff::Status huff_ctx::collect_timing() {
 
 huff::Status huff_ctx::sync() {
     HIP_TRY(hipStreamSynchronize(stream));
+    return huff::Status::ok();
+}
+
+huff::Status huff_ctx::aligned_stream(const uint8_t** d_comp, uint64_t comp_bytes) {
+    if (!(reinterpret_cast<uintptr_t>(*d_comp) & 15)) return huff::Status::ok();
+    HUFF_TRY(d_comp_align.ensure(comp_bytes + 64));
+    HIP_TRY(hipMemcpyAsync(d_comp_align.p, *d_comp, comp_bytes, hipMemcpyDeviceToDevice, stream));
+    *d_comp = static_cast<const uint8_t*>(d_comp_align.p);
     return huff::Status::ok();
 }
 
@@ -1096,342 +1103,6 @@ Status parse_block_size(const char* s, size_t* out) {
     else return Status::err(HUFF_E_INVALID_ARG, "Invalid block size");
     *out = static_cast<size_t>(v * m);
     return Status::ok();
-}
-
-}  // namespace huff
-
-// ---------------------------------------------------------------------------
-// index-free decode
-// ---------------------------------------------------------------------------
-
-huff::IndexlessSync& huff_ctx::indexless_ws() {
-    if (!idx_ws) idx_ws = std::make_shared<huff::IndexlessSync>();
-    return *idx_ws;
-}
-
-namespace huff {
-
-Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t valid_bits,
-                      const huff_tree* t, IndexlessSync& st, bool need_off,
-                      const std::function<Status()>& before_wait) {
-    const DecTables* dt = st.dt;
-    // segment length: a multiple of the gcd of all code lengths
-    uint32_t g = 0, lo_, hi_;
-    t->t.depth_range(&lo_, &hi_, &g);
-    if (g == 0) g = 1;
-    // codes <= 32 bits take the LDS-staged kernels, longer codes 2048-bit segments
-    // (~992 bits: with the one 8 KiB walk table a workgroup's LDS stays under
-    // 40 KiB, 4 workgroups per CU; 1024-bit segments measured ~1.5 % slower)
-#ifndef HUFF_SEG_TARGET
-#define HUFF_SEG_TARGET 992
-#endif
-    const uint64_t seg_target = dt->maxdepth <= 32 ? HUFF_SEG_TARGET : 2048;
-    uint64_t S = static_cast<uint64_t>(g) * ((seg_target + g - 1) / g);
-    // the LDS-staged kernels read lane i's bits from dword ~S/32 * i: with an
-    // even dword stride every lane starts on the same few banks (1024 bits: all
-    // 32 lanes of a half-wave on one bank); prefer an odd stride (S = 32 mod 64)
-    for (uint64_t k = (seg_target + g - 1) / g, tries = 0; tries < 128; ++k, ++tries)
-        if ((static_cast<uint64_t>(g) * k) % 64 == 32) {
-            S = static_cast<uint64_t>(g) * k;
-            break;
-        }
-    // the staged kernels' sample words hold 10-bit offsets (indexless.hip)
-    if (dt->maxdepth <= 32 && S >= 1024) S = static_cast<uint64_t>(g) * (1023 / g);
-    const uint64_t nseg = (valid_bits + S - 1) / S;
-    if (nseg > 0xFFFFFFFFull) return Status::err(HUFF_E_INVALID_ARG, "stream too long for one decode");
-    HUFF_TRY(st.s.ensure(nseg * 8));
-    HUFF_TRY(st.x0.ensure(nseg * 8));
-    HUFF_TRY(st.c.ensure(nseg * 8));
-    HUFF_TRY(st.off.ensure((nseg + 1) * 8));
-    HUFF_TRY(st.tm.ensure(nseg * 4));
-    HUFF_TRY(st.dl.ensure(nseg * 4));
-    HUFF_TRY(st.flag.ensure(32));  // kFixRounds + 4 words, zeroed by one aligned fill
-    const uint64_t nwg = (nseg + 255) / 256;  // workgroups of the staged speculative pass
-    HUFF_TRY(st.wtot.ensure(nwg * 8));
-    HUFF_TRY(st.woff.ensure((nwg + 1) * 8));
-    dev::IndexlessArgs& a = st.a;
-    a = dev::IndexlessArgs{};
-    a.comp = d_comp;
-    a.comp_bytes = comp_bytes;
-    a.valid_bits = valid_bits;
-    a.seg_bits = S;
-    // in phase with the segment starts; longer for codes past the walk table
-    a.lead_bits = (dt->maxdepth > dt->sbits ? dev::kLeadBitsLong : dev::kLeadBits) / g * g;
-    a.nseg = nseg;
-    a.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
-    a.lut_bits = dt->bits;
-    a.s = static_cast<uint64_t*>(st.s.p);
-    a.x = static_cast<uint64_t*>(st.x0.p);
-    a.c = static_cast<uint64_t*>(st.c.p);
-    a.max_len = dt->maxdepth;
-    a.stab = ctx->lut_u16(dt->soff);
-    a.stab_bits = dt->sbits;
-    a.wtab = ctx->lut_u16(dt->woff);
-    if (dt->l2words && !l2_table_disabled()) {  // else the global secondary tables
-        a.l2 = static_cast<const uint32_t*>(ctx->d_lut.p) + dt->l2off;
-        a.l2_words = dt->l2words;
-        a.l2_e = dt->l2E;
-        a.l2_dense = dt->l2dense ? 1u : 0u;
-    }
-    a.tm = static_cast<uint32_t*>(st.tm.p);
-    a.dl = static_cast<int32_t*>(st.dl.p);
-    a.flags = static_cast<unsigned int*>(st.flag.p);
-#ifdef HUFF_STAMPS
-    a.stamps = stamp_region(0);
-#endif
-    hipStream_t strm = ctx->stream;
-    if (dev::indexless_staged(a)) {  // speculative samples for the marking pass
-        a.nsamp = std::min<uint32_t>(dev::kSampMax, static_cast<uint32_t>((S - 1) / dev::kSampBits));
-        HUFF_TRY(st.samp.ensure(nseg * ((dev::kSampMax + 1) & ~1u) * 2 + 16));  // u16 slots, whole dwords per segment
-        a.samp = static_cast<uint16_t*>(st.samp.p);
-        HUFF_TRY(st.fixlist.ensure(nseg * 4 + 4));
-        a.fixlist = static_cast<uint32_t*>(st.fixlist.p);
-        HUFF_TRY(st.chain.ensure(nseg * 8 + 8));
-        a.chain = static_cast<uint32_t*>(st.chain.p);
-        HUFF_TRY(st.rec.ensure(nseg * 8));
-        a.rec = static_cast<uint64_t*>(st.rec.p);
-        a.wtot = static_cast<unsigned long long*>(st.wtot.p);
-    } else {  // k_spec leaves the merge record to the fix-up rounds
-        HIP_TRY(hipMemsetAsync(st.tm.p, 0, nseg * 4, strm));
-        HIP_TRY(hipMemsetAsync(st.dl.p, 0, nseg * 4, strm));
-    }
-    static_assert((dev::kFixRounds + 4) * 4 <= 32, "the flags fit the zeroed 32 bytes");
-    HIP_TRY(hipMemsetAsync(st.flag.p, 0, 32, strm));
-    HIP_TRY(dev::launch_indexless_spec(a, strm));
-    // fix-up rounds and the sequential fallback decide on the device whether
-    // they have work (no host wait between rounds)
-    HIP_TRY(dev::launch_indexless_settle_all(a, strm));
-    HUFF_TRY(st.tsum.ensure((nseg / 1024 + 2) * 8));
-    st.total = 0;
-    // the staged pass keeps per-workgroup counts: only they are scanned
-    // (k_mark_lite scans inside a workgroup), unless a consumer needs every
-    // segment's offset (the walked marks, k_emit)
-    st.block_off = a.wtot && !need_off;
-    // the total goes from the scan's last kernel straight to pinned host
-    // memory, tagged; the host polls it (a copy and a stream
-    // synchronisation here cost ~40 us between the sync and the decode)
-    dev::HistDone done;
-    HUFF_TRY(ctx->total.arm(1, &done));
-    if (st.block_off) {
-        HIP_TRY(dev::launch_scan(static_cast<const uint64_t*>(st.wtot.p), static_cast<uint32_t>(nwg), 0,
-                                 static_cast<uint64_t*>(st.woff.p), static_cast<uint64_t*>(st.tsum.p), strm, done));
-    } else {
-        if (a.rec) HIP_TRY(dev::launch_indexless_counts(a, strm));  // the staged pass packs its counts
-        HIP_TRY(dev::launch_scan(static_cast<const uint64_t*>(st.c.p), static_cast<uint32_t>(nseg), 0,
-                                 static_cast<uint64_t*>(st.off.p), static_cast<uint64_t*>(st.tsum.p), strm, done));
-    }
-    if (before_wait) HUFF_TRY(before_wait());
-    HUFF_TRY(ctx->total.wait(strm, done.tag, &st.total, 1, "the index-free scan finished without publishing its total"));
-    if (std::getenv("HUFF_FIX_STATS")) {  // diagnostics: how much the fix-up did (a synchronising copy)
-        unsigned int f[8];
-        HIP_TRY(hipMemcpyAsync(f, st.flag.p, sizeof f, hipMemcpyDeviceToHost, strm));
-        HIP_TRY(hipStreamSynchronize(strm));
-        static_assert(dev::kFixRounds == 4, "the line below prints four round flags");
-        std::fprintf(stderr,
-                     "huff fix-up: segments %llu, listed by the speculative pass %u, chain fixes %u, "
-                     "segment bits %llu, rounds %u %u %u %u\n",
-                     static_cast<unsigned long long>(nseg), f[dev::kFixRounds], f[dev::kFixRounds + 3],
-                     static_cast<unsigned long long>(S), f[0], f[1], f[2], f[3]);
-    }
-    return Status::ok();
-}
-
-Status indexless_mark(huff_ctx* ctx, IndexlessSync& st, DevBuf& sub_abs, uint32_t shift) {
-    HUFF_TRY(sub_abs.ensure(((st.total + (1ull << shift) - 1) >> shift) * 8 + 8));
-    HIP_TRY(dev::launch_indexless_mark(st.a, static_cast<const uint64_t*>(st.off.p),
-                                       static_cast<uint64_t*>(sub_abs.p), shift, ctx->stream));
-    return Status::ok();
-}
-
-Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t valid_bits,
-                            const huff_tree* t, DevBuf& out, uint64_t* nsym, uint8_t* d_user, size_t user_cap,
-                            unsigned long long* d_end) {
-    *nsym = 0;
-    // the output goes to d_user when given (capacity checked once the count
-    // is known), else into `out`
-    auto out_ptr = [&](uint64_t need) -> Status {
-        if (d_user) {
-            if (need > user_cap) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
-            return Status::ok();
-        }
-        return out.ensure(need + 16);
-    };
-    auto out_at = [&]() { return d_user ? d_user : static_cast<uint8_t*>(out.p); };
-    if (valid_bits == 0) return Status::ok();
-    HUFF_TRY(ctx->activate());
-    if (reinterpret_cast<uintptr_t>(d_comp) & 15) {
-        // the staged kernels read the stream in 16-B pieces: a stream at any
-        // other alignment (a tensor view) is copied once to an aligned buffer
-        HUFF_TRY(ctx->d_comp_align.ensure(comp_bytes + 64));
-        HIP_TRY(hipMemcpyAsync(ctx->d_comp_align.p, d_comp, comp_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_comp = static_cast<const uint8_t*>(ctx->d_comp_align.p);
-    }
-    const DecTables* dt = nullptr;
-    HUFF_TRY(ctx->upload_dec_tables(t, &dt));
-    // the window end (d_end): `count` codes walked from a known boundary
-    auto walk_end = [&](const uint64_t* start, uint64_t start_v, const uint64_t* count, uint64_t count_v,
-                        bool packed = false) -> Status {
-        if (!d_end) return Status::ok();
-        dev::WalkEndArgs w{};
-        w.start_packed = packed ? 1u : 0u;
-        w.comp = d_comp;
-        w.comp_bytes = comp_bytes;
-        w.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
-        w.lut_bits = dt->bits;
-        w.start = start;
-        w.start_v = start_v;
-        w.count = count;
-        w.count_v = count_v;
-        w.end = d_end;
-        HIP_TRY(dev::launch_walk_end(w, ctx->stream));
-        return Status::ok();
-    };
-    if (dt->all8 && !fixed8_disabled()) {  // every code 8 bits: one symbol per whole byte
-        const uint64_t n = valid_bits / 8;
-        *nsym = n;
-        HUFF_TRY(walk_end(nullptr, 8 * n, nullptr, 0));
-        HUFF_TRY(out_ptr(n));
-        dev::BytemapArgs m{};
-        m.src = d_comp;
-        m.dst = out_at();
-        m.n = n;
-        for (int b = 0; b < 256; ++b) m.map[b] = static_cast<uint8_t>(dt->lut[b]);
-        HIP_TRY(dev::launch_bytemap(m, ctx->stream));
-        return Status::ok();
-    }
-    if (dt->maxdepth > dev::kLongMaxLen) {  // deep codes: one lane walks the stream (deep.hip)
-        DevBuf& cnt = ctx->idx_sub_abs;
-        HUFF_TRY(cnt.ensure(8));
-        dev::DeepSerialArgs d{};
-        d.comp = d_comp;
-        d.comp_bytes = comp_bytes;
-        d.valid_bits = valid_bits;
-        d.lut = static_cast<const uint32_t*>(ctx->d_lut.p);
-        d.lut_bits = dt->bits;
-        d.out = d_user;
-        d.cap = d_user ? user_cap : 0;
-        d.count = static_cast<unsigned long long*>(cnt.p);
-        d.end = d_end;
-        HIP_TRY(dev::launch_decode_deep_serial(d, ctx->stream));  // counts (and writes, when d_user is given)
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HUFF_TRY(ctx->sync());
-        *nsym = total;
-        HUFF_TRY(out_ptr(total));
-        if (!d_user) {  // into `out`, now that its size is known
-            d.out = static_cast<uint8_t*>(out.p);
-            d.cap = total;
-            HIP_TRY(dev::launch_decode_deep_serial(d, ctx->stream));
-        }
-        HIP_TRY(hipEventRecord(ctx->lut_free, ctx->stream));
-        return Status::ok();
-    }
-    const uint32_t check = decode_check_mode();
-    IndexlessSync& st = ctx->indexless_ws();
-    st.dt = dt;
-    // with a caller's buffer, the marks go out before the host waits for the
-    // count: sub_abs sized for the most symbols the stream or the buffer can
-    // hold (shortest code), k_mark_lite bounded to it (22 us of idle stream
-    // between the scan and k_mark_lite otherwise)
-    bool marked = false;
-    // the compact marks (u32 per 64 symbols + u32 per task: dev::mark32_*)
-    // unless a consumer wants absolute u64 marks (the window end of the file
-    // path, the check build)
-    const bool compact = !check && !d_end;
-    auto mark_early = [&]() -> Status {
-        if (!d_user || check || d_end || !st.block_off || !dev::indexless_staged(st.a)) return Status::ok();
-        uint32_t min_len = 64, max_len_;
-        t->t.depth_range(&min_len, &max_len_);
-        const uint64_t most = std::min<uint64_t>(user_cap, valid_bits / min_len);
-        const uint64_t runs = (most + 63) >> 6;
-        HUFF_TRY(ctx->idx_mark32.ensure(runs * 4 + 8));
-        HUFF_TRY(ctx->idx_task_seg.ensure(((most + dev::kTaskSym - 1) / dev::kTaskSym) * 4 + 8));
-        HIP_TRY(dev::launch_indexless_mark_lite(st.a, nullptr, static_cast<const unsigned long long*>(st.woff.p),
-                                                nullptr, runs, ctx->stream, static_cast<uint32_t*>(ctx->idx_mark32.p),
-                                                static_cast<uint32_t*>(ctx->idx_task_seg.p)));
-        marked = true;
-        return Status::ok();
-    };
-    // k_emit (codes > 32 bits) and the walked marks of the check build read every segment's offset
-    HUFF_TRY(indexless_sync(ctx, d_comp, comp_bytes, valid_bits, t, st, check != 0, mark_early));
-    const uint64_t total = st.total;
-    *nsym = total;
-    if (total == 0) HUFF_TRY(walk_end(nullptr, 0, nullptr, 0));
-    HUFF_TRY(out_ptr(total));
-    hipStream_t strm = ctx->stream;
-    if (total == 0) {
-        // no letter to write. (The staged pass leaves st.a.s / c and st.off
-        // unwritten: k_emit below would read what an earlier decode of codes
-        // past 32 bits left there and write that many letters to the output,
-        // which for a count-only query is not even a buffer.)
-        HIP_TRY(hipEventRecord(ctx->lut_free, strm));
-        return Status::ok();
-    }
-    if (dev::indexless_staged(st.a) && !(reinterpret_cast<uintptr_t>(d_comp) & 15)) {
-        // a misaligned output: decoded into an aligned buffer, then copied (as huff_enc::decode)
-        const bool bounce = reinterpret_cast<uintptr_t>(out_at()) & 15;
-        if (bounce) HUFF_TRY(ctx->d_align.ensure(total + 64));
-        // a restart point every 64 symbols, then the fixed-count decoder
-        // (k_mark_lite: a boundary and the codes to skip from it, the
-        // decoder's lanes walk those codes themselves; the self-check builds,
-        // HUFF_DEC_VARIANT=11, needs exact lane starts: k_mark_lds walks)
-        DevBuf& sub_abs = ctx->idx_sub_abs;
-        if (check) {
-            HUFF_TRY(indexless_mark(ctx, st, sub_abs, 6));
-        } else if (!marked && compact) {
-            HUFF_TRY(ctx->idx_mark32.ensure(((total + 63) >> 6) * 4 + 8));
-            HUFF_TRY(ctx->idx_task_seg.ensure(((total + dev::kTaskSym - 1) / dev::kTaskSym) * 4 + 8));
-            HIP_TRY(dev::launch_indexless_mark_lite(
-                st.a, st.block_off ? nullptr : static_cast<const uint64_t*>(st.off.p),
-                st.block_off ? static_cast<const unsigned long long*>(st.woff.p) : nullptr, nullptr, ~0ull, strm,
-                static_cast<uint32_t*>(ctx->idx_mark32.p), static_cast<uint32_t*>(ctx->idx_task_seg.p)));
-        } else if (!marked) {
-            HUFF_TRY(sub_abs.ensure(((total + 63) >> 6) * 8 + 8));
-            HIP_TRY(dev::launch_indexless_mark_lite(
-                st.a, st.block_off ? nullptr : static_cast<const uint64_t*>(st.off.p),
-                st.block_off ? static_cast<const unsigned long long*>(st.woff.p) : nullptr,
-                static_cast<uint64_t*>(sub_abs.p), ~0ull, strm));
-        }
-        const uint64_t m = ((total - 1) >> 6) << 6;  // the last mark: symbol m
-        if (!compact)  // (d_end never goes with the compact marks)
-            HUFF_TRY(walk_end(static_cast<const uint64_t*>(sub_abs.p) + (m >> 6), 0, nullptr, total - m, !check));
-        dev::DecodeArgs d{};
-        d.comp = d_comp;
-        d.comp_bytes = comp_bytes;
-        fill_fixed_decode(d, ctx, dt, valid_bits, total);
-        d.sub_abs64 = compact ? nullptr : static_cast<const uint64_t*>(sub_abs.p);
-        d.mark32 = compact ? static_cast<const uint32_t*>(ctx->idx_mark32.p) : nullptr;
-        d.task_seg = compact ? static_cast<const uint32_t*>(ctx->idx_task_seg.p) : nullptr;
-        d.seg_bits = static_cast<uint32_t>(st.a.seg_bits);
-        d.skip_packed = check ? 0u : 1u;
-        d.end_bit = valid_bits;
-        d.nchunks = static_cast<uint32_t>((total + dev::kChunk - 1) / dev::kChunk);
-        d.out = bounce ? static_cast<uint8_t*>(ctx->d_align.p) : out_at();
-        d.check_mode = check;
-        HUFF_TRY(run_checked_decode(ctx, d, [&] { return dev::launch_decode_fixed(d, strm); }));
-        HIP_TRY(hipEventRecord(ctx->lut_free, strm));
-        if (bounce) HIP_TRY(hipMemcpyAsync(out_at(), ctx->d_align.p, total, hipMemcpyDeviceToDevice, strm));
-        return Status::ok();
-    }
-    HIP_TRY(dev::launch_indexless_emit(st.a, static_cast<const uint64_t*>(st.off.p), out_at(), strm));
-    if (total)  // the last segment's codes from its settled start
-        HUFF_TRY(walk_end(st.a.s + st.a.nseg - 1, 0, st.a.c + st.a.nseg - 1, 0));
-    HIP_TRY(hipEventRecord(ctx->lut_free, strm));
-    return Status::ok();
-}
-
-Status decode_indexless_host(huff_ctx* ctx, const uint8_t* comp, size_t len, uint64_t valid_bits, const huff_tree* t,
-                             std::vector<uint8_t>& out) {
-    out.clear();
-    HUFF_TRY(ctx->activate());
-    DevBuf d_comp, d_out;
-    HUFF_TRY(d_comp.ensure(len + 16));
-    HIP_TRY(hipMemcpyAsync(d_comp.p, comp, len, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t n = 0;
-    HUFF_TRY(decode_indexless_dev(ctx, static_cast<const uint8_t*>(d_comp.p), len, valid_bits, t, d_out, &n));
-    out.resize(n);
-    if (n) HIP_TRY(hipMemcpyAsync(out.data(), d_out.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    return ctx->sync();
 }
 
 }  // namespace huff

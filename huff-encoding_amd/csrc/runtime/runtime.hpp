@@ -130,7 +130,7 @@ struct TaggedWords {
 };
 
 namespace huff {
-struct IndexlessSync;
+struct IndexlessStep;
 struct FileWs;
 }
 
@@ -158,14 +158,14 @@ struct huff_ctx {
         return reinterpret_cast<const uint16_t*>(static_cast<const uint32_t*>(d_lut.p) + off);
     }
     DevBuf d_align;      // aligned decode target for a misaligned output pointer
-    DevBuf d_comp_align; // aligned copy of a misaligned index-free input stream
+    // the index-free and wide decoders read the stream in dwords and 16-B pieces: at any
+    // other alignment (a tensor view) it is copied once to d_comp_align, and *d_comp set to that
+    DevBuf d_comp_align;
+    huff::Status aligned_stream(const uint8_t** d_comp, uint64_t comp_bytes);
     DevBuf d_err;        // k_decode_fixed self-check record (check builds)
-    // index-free decode workspace, kept across calls (per-call allocations
-    // of its ~100 MB per GiB of stream cost more than the kernels)
-    std::shared_ptr<huff::IndexlessSync> idx_ws;
-    DevBuf idx_sub_abs;
-    DevBuf idx_mark32, idx_task_seg;  // the index-free decode's compact marks (k_mark_lite)
-    huff::IndexlessSync& indexless_ws();
+    // the index-free decode's step and workspace (indexless_rt.hpp)
+    std::shared_ptr<huff::IndexlessStep> idx_ws;
+    huff::IndexlessStep& indexless_ws();
     // the .hff file path's pinned pieces and device buffers (filepath.cpp),
     // kept across calls: pinning ~0.5 GB per call costs more than the copies
     std::shared_ptr<huff::FileWs> file_ws;
@@ -275,33 +275,10 @@ Status file_compress(huff_ctx* ctx, const char* src, const char* dst, size_t blo
 Status file_decompress(huff_ctx* ctx, const char* src, const char* dst, size_t block_size);
 Status parse_block_size(const char* s, size_t* out);
 Status run_checked_decode(huff_ctx* ctx, dev::DecodeArgs& a, const std::function<hipError_t()>& launch);
-// decode without a restart index: valid_bits of the stream at d_comp; the
-// symbols land in `out` (grown as needed), their count in *nsym
-Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t valid_bits,
-                            const huff_tree* t, DevBuf& out, uint64_t* nsym, uint8_t* d_user = nullptr,
-                            size_t user_cap = 0, unsigned long long* d_end = nullptr);
-// (d_end, device: the bit after the last complete code, for a window of a
-// longer stream)
-// the self-synchronising part of the index-free decode (spec, fix, scan):
-// symbol offsets per segment in `off`, the symbol count in `total`
-struct IndexlessSync {
-    const DecTables* dt = nullptr;  // tables of the tree, uploaded to ctx->d_lut
-    DevBuf s, x0, c, off, flag, tsum, samp, tm, dl, fixlist, chain, rec;
-    DevBuf wtot, woff;  // per-workgroup code counts of the staged pass and their exclusive scan
-    dev::IndexlessArgs a{};
-    uint64_t total = 0;
-    bool block_off = false;  // offsets per workgroup (woff) only; off[] not written
-};
-// need_off: every segment's offset in `off` (else, on the staged path, only
-// the per-workgroup offsets in `woff`: k_mark_lite's form)
-// before_wait: launched after the scan, before the host waits for the
-// total (work that does not need the count: k_mark_lite, so the host's wait
-// overlaps it instead of stalling the stream)
-Status indexless_sync(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t valid_bits,
-                      const huff_tree* t, IndexlessSync& st, bool need_off = true,
-                      const std::function<Status()>& before_wait = nullptr);
-// sub_abs[g] = first bit of symbol g << shift (needs dev::indexless_staged(st.a))
-Status indexless_mark(huff_ctx* ctx, IndexlessSync& st, DevBuf& sub_abs, uint32_t shift = 8);
-Status decode_indexless_host(huff_ctx* ctx, const uint8_t* comp, size_t len, uint64_t valid_bits,
-                             const huff_tree* t, std::vector<uint8_t>& out);
+// the k_decode_fixed part of DecodeArgs: the tables uploaded to d_lut, and
+// the stage and refill choices for a stream of `bits` bits holding n letters
+void fill_fixed_decode(dev::DecodeArgs& a, const huff_ctx* ctx, const DecTables* dt, uint64_t bits, uint64_t n);
+#ifdef HUFF_STAMPS
+uint64_t* stamp_region(int r);  // timing builds only (runtime.cpp)
+#endif
 }  // namespace huff

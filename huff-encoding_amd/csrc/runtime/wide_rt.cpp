@@ -2,6 +2,8 @@
 // (wide_rt.hpp; kernels in device/wide.hip, device/wweights.hip).
 #include "wide_rt.hpp"
 
+#include "indexless_rt.hpp"
+
 #include <atomic>
 #include <cstring>
 
@@ -159,14 +161,7 @@ Status huff_wenc::upload_dec(const huff_wtree* t) {
 Status huff_wenc::decode(const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes, uint8_t* d_out,
                          const uint64_t* sub_abs, bool skip_packed) {
     HUFF_TRY(ctx->activate());
-    if (reinterpret_cast<uintptr_t>(d_comp) & 15) {
-        // the decoders read the stream in dwords and 16-B pieces: a stream at
-        // any other alignment (packed into a tensor view at an odd offset,
-        // which huff_wenc_pack allows) is copied once to an aligned buffer
-        HUFF_TRY(ctx->d_comp_align.ensure(comp_bytes + 64));
-        HIP_TRY(hipMemcpyAsync(ctx->d_comp_align.p, d_comp, comp_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_comp = static_cast<const uint8_t*>(ctx->d_comp_align.p);
-    }
+    HUFF_TRY(ctx->aligned_stream(&d_comp, comp_bytes));  // (huff_wenc_pack allows a stream at an odd offset)
     HUFF_TRY(upload_dec(t));
     huff::dev::WideDecArgs a{};
     a.comp = d_comp;
@@ -379,62 +374,31 @@ Status wdecode_indexless_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* 
                              uint64_t valid_bits, uint8_t* d_out, size_t cap_letters, uint64_t* n_out) {
     *n_out = 0;
     if (valid_bits == 0) return Status::ok();
-    HUFF_TRY(ctx->activate());
-    if (reinterpret_cast<uintptr_t>(d_comp) & 15) {  // the sync kernels stage 16-B pieces: an aligned copy
-        HUFF_TRY(ctx->d_comp_align.ensure(comp_bytes + 64));
-        HIP_TRY(hipMemcpyAsync(ctx->d_comp_align.p, d_comp, comp_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        d_comp = static_cast<const uint8_t*>(ctx->d_comp_align.p);
-    }
     // synchronise on the tree's shape (the sync kernels only use code lengths)
-    const huff_tree* shape = t->shape_tree();
-    const DecTables* dt = nullptr;
-    HUFF_TRY(ctx->upload_dec_tables(shape, &dt));
-    IndexlessSync& st = ctx->indexless_ws();
-    st.dt = dt;
+    IndexlessStep& st = ctx->indexless_ws();
+    HUFF_TRY(st.open(ctx, t->shape_tree(), d_comp, comp_bytes, valid_bits));
     const WideDecTables* wdt = nullptr;
     HUFF_TRY(t->dec_tables(&wdt));
-    const bool skip = !wdt->stab.empty() && !wide_mark_walk();
-    DevBuf& sub_abs = ctx->idx_sub_abs;
     // every kWideRun-th letter: the task decoder (the tree's two-level table)
-    // takes k_mark_lite's marks (a boundary and the codes to skip from it, as
-    // the byte path's skip build), launched before the host waits for the
-    // count (sized for the most letters the buffer or the stream holds);
-    // HUFF_WIDE_MARK_WALK=1 or the long-code decoder: exact points walked by
-    // k_mark_lds
-    bool marked = false;
-    auto mark_early = [&]() -> Status {
-        if (!skip || !d_out || !st.block_off || !dev::indexless_staged(st.a)) return Status::ok();
-        uint32_t min_len = 64, max_len_;
-        shape->t.depth_range(&min_len, &max_len_);
-        const uint64_t runs = (std::min<uint64_t>(cap_letters, valid_bits / min_len) + 63) >> 6;
-        HUFF_TRY(sub_abs.ensure(runs * 8 + 8));
-        HIP_TRY(dev::launch_indexless_mark_lite(st.a, nullptr, static_cast<const unsigned long long*>(st.woff.p),
-                                                static_cast<uint64_t*>(sub_abs.p), runs, ctx->stream));
-        marked = true;
-        return Status::ok();
-    };
-    HUFF_TRY(indexless_sync(ctx, d_comp, comp_bytes, valid_bits, shape, st, !skip, mark_early));
+    // takes k_mark_lite's skip marks, as the byte path's skip build, queued
+    // before the count is known when there is a buffer; HUFF_WIDE_MARK_WALK=1
+    // or the long-code decoder: exact points walked by k_mark_lds
+    const bool skip = !wdt->stab.empty() && !wide_mark_walk();
+    HUFF_TRY(st.count(skip ? MarkForm::Skip : MarkForm::Walked,
+                      d_out ? std::optional<uint64_t>(cap_letters) : std::nullopt));
     *n_out = st.total;
     if (!d_out) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
     if (st.total > cap_letters) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
-    if (!dev::indexless_staged(st.a))
+    if (!st.staged())
         return Status::err(HUFF_E_CODE_TOO_LONG, "index-free decode of letters wider than a byte needs codes <= 32 bits");
-    if (skip && !marked) {
-        HUFF_TRY(sub_abs.ensure(((st.total + 63) >> 6) * 8 + 8));
-        HIP_TRY(dev::launch_indexless_mark_lite(
-            st.a, st.block_off ? nullptr : static_cast<const uint64_t*>(st.off.p),
-            st.block_off ? static_cast<const unsigned long long*>(st.woff.p) : nullptr,
-            static_cast<uint64_t*>(sub_abs.p), ~0ull, ctx->stream));
-    } else if (!skip) {
-        HUFF_TRY(indexless_mark(ctx, st, sub_abs, 6));
-    }
+    HUFF_TRY(st.marks());
     HIP_TRY(hipEventRecord(ctx->lut_free, ctx->stream));
     // one task decoder per context: its buffers only grow and its tables
     // upload once per tree (a fresh one per call allocated and freed ~40 MB)
     if (!ctx->wdec_ws) ctx->wdec_ws = std::make_shared<huff_wenc>();
     huff_wenc& e = *ctx->wdec_ws;
     HUFF_TRY(e.init(ctx, t->t.width(), nullptr, st.total));
-    HUFF_TRY(e.decode(t, d_comp, comp_bytes, d_out, static_cast<const uint64_t*>(sub_abs.p), skip));
+    HUFF_TRY(e.decode(t, st.a.comp, comp_bytes, d_out, st.sub_abs64, skip));
     return ctx->sync();
 }
 

@@ -2,7 +2,7 @@
 """Per-phase wave budgets from in-kernel s_memtime stamps (timing build).
 
     tools/build_variant.sh stamps "-DHUFF_STAMPS" csrc/device/indexless.hip \
-        csrc/device/decode_wave.hip csrc/runtime/runtime.cpp
+        csrc/device/decode_wave.hip csrc/runtime/runtime.cpp csrc/runtime/indexless_rt.cpp
     HUFF_LIB_AB=stamps python tools/stamps.py --workload zipf
 
 Runs the indexed decode and the index-free decode of a 1 GiB stream once
@@ -82,7 +82,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="zipf", choices=sorted(SEEDS))
     ap.add_argument("--bytes", type=int, default=1 << 30)
-    ap.add_argument("--seg", type=int, default=992, help="segment bits of the build (runtime.cpp HUFF_SEG_TARGET)")
+    ap.add_argument("--seg", type=int, default=992, help="segment bits of the build (host/indexless_plan.hpp HUFF_SEG_TARGET)")
     ap.add_argument("--walks", type=int, default=1, help="segments per thread of k_spec_lds")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -113,7 +113,7 @@ def main():
     # the last index-free call left regions 0 and 1; the indexed decode region 2
     job.decode(tree, out.data_ptr(), dec.data_ptr())
     torch.cuda.synchronize()
-    # segments of the speculative pass: runtime.cpp indexless_sync (args.seg bits for these trees)
+    # segments of the speculative pass: host/indexless_plan.hpp (args.seg bits for these trees)
     nseg = (bits + args.seg - 1) // args.seg
     per_wg = 256 * args.walks
     kernels = (("k_spec_lds", 0, (nseg + per_wg - 1) // per_wg * 4), ("k_decode_fixed_skip", 1, ntasks),
