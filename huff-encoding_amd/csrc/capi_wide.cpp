@@ -295,6 +295,25 @@ int huff_wenc_decode(huff_wenc* e, const huff_wtree* t, const uint8_t* d_comp, u
     });
 }
 
+int huff_wenc_decode_ranges(huff_wenc* e, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                            const uint64_t* first, const uint64_t* count, const uint64_t* out_begin,
+                            uint32_t nreq, void* d_out, size_t out_cap_letters, uint32_t* status) {
+    if (!e || !t || !d_comp || (nreq && (!first || !count || !out_begin || !status)) || (!d_out && out_cap_letters))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return e->decode_ranges(t, d_comp, comp_bytes, first, count, out_begin, nreq, static_cast<uint8_t*>(d_out),
+                                out_cap_letters, status);
+    });
+}
+
+int huff_wdecompress_range(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count, void* out,
+                           size_t cap_letters) {
+    if (!ctx || !cd || (!out && cap_letters)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return huff::wdecompress_range_host(ctx, cd, first, count, static_cast<uint8_t*>(out), cap_letters);
+    });
+}
+
 int huff_dev_wdecompress(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
                          uint8_t padding, void* d_out, size_t out_cap_letters, size_t* n_out) {
     if (!ctx || !t || !n_out || (!d_comp && comp_bytes)) return fail(HUFF_E_INVALID_ARG, "null argument");
@@ -316,6 +335,9 @@ uint64_t huff_diag_wide_build_launches(uint32_t i) { return huff::dev::wide_buil
 uint32_t huff_diag_wide_index_forms(void) { return huff::dev::wide_index_forms(); }
 const char* huff_diag_wide_index_form_name(uint32_t i) { return huff::dev::wide_index_form_name(i); }
 uint64_t huff_diag_wide_index_form_launches(uint32_t i) { return huff::dev::wide_index_form_launches(i); }
+uint32_t huff_diag_wrange_builds(void) { return huff::dev::wide_range_builds(); }
+const char* huff_diag_wrange_build_name(uint32_t i) { return huff::dev::wide_range_build_name(i); }
+uint64_t huff_diag_wrange_build_launches(uint32_t i) { return huff::dev::wide_range_build_launches(i); }
 
 int huff_wtree_diag(const huff_wtree* t, uint64_t out[HUFF_WTREE_DIAG_WORDS]) {
     if (!t || !out) return fail(HUFF_E_INVALID_ARG, "null argument");

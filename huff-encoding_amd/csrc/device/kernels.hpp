@@ -645,6 +645,35 @@ hipError_t launch_decode_ranges(const RangesArgs& a, hipStream_t s);
 uint32_t decode_ranges_index_forms();
 const char* decode_ranges_index_form_name(uint32_t i);
 uint64_t decode_ranges_index_form_launches(uint32_t i);
+// Letter ranges of one indexed wide-letter stream (wdecode_ranges.hip): the
+// requests as above, first, count and out_begin in letters of `width` bytes;
+// the index is the wide job's chunk_start (per kWideChunk letters) + sub_bit
+// (per kWideRun letters), the table WideDecArgs::lut with its leaf letters.
+struct WRangesArgs {
+    const uint8_t* comp;          // 4-B aligned
+    uint64_t comp_bytes;
+    const uint32_t* lut;          // WideDecArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint8_t* letters;       // [nleaves * width], readable in whole dwords
+    uint32_t nleaves;
+    uint32_t width;               // 1, 2, 4, 8, 16
+    const uint64_t* chunk_start;  // [nchunks + 1]
+    const uint32_t* sub_bit;      // [ceil(n / kWideRun)]
+    uint32_t nchunks;
+    uint64_t n;
+    const RangeReq* req;
+    uint32_t nreq;                // >= 1
+    uint64_t npieces;
+    uint8_t* out;                 // aligned to min(width, 16)
+    uint32_t* status;             // zeroed; atomicMax of kBatchCorrupt
+};
+hipError_t launch_wide_decode_ranges(const WRangesArgs& a, hipStream_t s);
+// diagnostics (huffgpu_wide.h huff_diag_wrange_*): the launcher's table of
+// compiled k_wdecode_ranges builds with process-wide launch counts. name: null
+// past the last row.
+uint32_t wide_range_builds();
+const char* wide_range_build_name(uint32_t i);
+uint64_t wide_range_build_launches(uint32_t i);
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

@@ -2,6 +2,7 @@
 // (wide_rt.hpp; kernels in device/wide.hip, device/wweights.hip).
 #include "wide_rt.hpp"
 
+#include "../host/range_plan.hpp"
 #include "indexless_rt.hpp"
 
 #include <atomic>
@@ -66,6 +67,7 @@ Status huff_wenc::init(huff_ctx* c, uint32_t w, const uint8_t* d, uint64_t nlett
     width = w;
     d_in = d;
     n = nletters;
+    index_uploaded = false;
     nchunks = static_cast<uint32_t>((n + huff::dev::kWideChunk - 1) / huff::dev::kWideChunk);
     HUFF_TRY(chunk_bits.ensure((nchunks + 1) * 8));
     HUFF_TRY(chunk_start.ensure((nchunks + 2) * 8));
@@ -120,6 +122,7 @@ Status huff_wenc::bits(const huff_wtree* t, uint64_t* total, huff::u128* missing
     HIP_TRY(hipMemcpyAsync(&hv[1], missing.p, 8, hipMemcpyDeviceToHost, s));
     HUFF_TRY(ctx->sync());
     bits_tree = 0;
+    index_uploaded = false;  // the index is this pass's now
     if (hv[1] != ~0ull) {  // comp.rs:426-432: the first letter (input order) with no code
         uint8_t lb[16] = {};
         HIP_TRY(hipMemcpy(lb, d_in + hv[1] * width, width, hipMemcpyDeviceToHost));
@@ -220,6 +223,68 @@ Status huff_wenc::upload_index(const huff_index_host& idx) {
     if (!idx.sub_bit.empty())
         HIP_TRY(hipMemcpyAsync(sub_bit.p, idx.sub_bit.data(), idx.sub_bit.size() * 4, hipMemcpyHostToDevice,
                                ctx->stream));
+    index_uploaded = true;
+    return Status::ok();
+}
+
+static_assert(huff::kRangeBlock == huff::dev::kWideRun, "host/range_plan.hpp's block is the wide index's run");
+
+Status huff_wenc::decode_ranges(const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes,
+                                const uint64_t* first, const uint64_t* count, const uint64_t* out_begin,
+                                uint32_t nreq, uint8_t* d_out, size_t out_cap_letters, uint32_t* status) {
+    if (reinterpret_cast<uintptr_t>(d_comp) & 3)
+        return Status::err(HUFF_E_INVALID_ARG, "compressed stream must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out) & (width - 1))  // width <= 16
+        return Status::err(HUFF_E_INVALID_ARG, "output must be aligned to the letter width");
+    if (t->t.width() != width) return Status::err(HUFF_E_INVALID_ARG, "the tree's letter width differs from the job's");
+    if (!index_uploaded) {
+        if (bits_tree == 0) return Status::err(HUFF_E_STATE, "no restart index: run pass A (or upload an index) first");
+        if (bits_tree != t->id)
+            return Status::err(HUFF_E_STATE, "decode tree differs from the tree of the job's pass A");
+    }
+    // the requests that pass both range checks and have letters, in the
+    // caller's order, each with its first piece of the launch
+    std::vector<huff::dev::RangeReq> req;
+    uint64_t npieces = 0;
+    for (uint32_t r = 0; r < nreq; ++r) {
+        const bool ok =
+            huff::range_inside(first[r], count[r], n) && huff::range_inside(out_begin[r], count[r], out_cap_letters);
+        status[r] = ok ? HUFF_OK : HUFF_E_INVALID_ARG;
+        if (!ok || count[r] == 0) continue;
+        req.push_back({first[r], count[r], out_begin[r], npieces, r, 0});
+        npieces += huff::range_pieces(first[r], count[r]);
+    }
+    if (req.empty()) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    HUFF_TRY(upload_dec(t));
+    HUFF_TRY(range_req.ensure(req.size() * sizeof(huff::dev::RangeReq)));
+    HUFF_TRY(range_status.ensure(static_cast<size_t>(nreq) * 4));
+    HIP_TRY(hipMemcpyAsync(range_req.p, req.data(), req.size() * sizeof(huff::dev::RangeReq), hipMemcpyHostToDevice,
+                           ctx->stream));
+    HIP_TRY(hipMemsetAsync(range_status.p, 0, static_cast<size_t>(nreq) * 4, ctx->stream));
+    huff::dev::WRangesArgs a{};
+    a.comp = d_comp;
+    a.comp_bytes = comp_bytes;
+    a.lut = static_cast<const uint32_t*>(lut.p);
+    a.lut_bits = dt->bits;
+    a.letters = static_cast<const uint8_t*>(letters.p);
+    a.nleaves = static_cast<uint32_t>(dt->letters.size() / width);
+    a.width = width;
+    a.chunk_start = static_cast<const uint64_t*>(chunk_start.p);
+    a.sub_bit = static_cast<const uint32_t*>(sub_bit.p);
+    a.nchunks = nchunks;
+    a.n = n;
+    a.req = static_cast<const huff::dev::RangeReq*>(range_req.p);
+    a.nreq = static_cast<uint32_t>(req.size());
+    a.npieces = npieces;
+    a.out = d_out;
+    a.status = static_cast<uint32_t*>(range_status.p);
+    HUFF_TRY(ctx->timed("wdecode_ranges", [&] { return huff::dev::launch_wide_decode_ranges(a, ctx->stream); }));
+    std::vector<uint32_t> st(nreq);
+    HIP_TRY(hipMemcpyAsync(st.data(), range_status.p, static_cast<size_t>(nreq) * 4, hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HUFF_TRY(ctx->sync());  // also: req has left the host
+    for (const auto& q : req) status[q.index] = st[q.index];
     return Status::ok();
 }
 
@@ -436,6 +501,42 @@ Status wdecompress_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint8_t* o
     HUFF_TRY(e.decode(cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(),
                       static_cast<uint8_t*>(ctx->d_out.p)));
     HIP_TRY(hipMemcpyAsync(out, ctx->d_out.p, n * W, hipMemcpyDeviceToHost, s));
+    return ctx->sync();
+}
+
+Status wdecompress_range_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count,
+                              uint8_t* out, size_t cap_letters) {
+    const uint32_t W = cd->tree->t.width();
+    if (!cd->index) {  // the slow route: everything (the self-synchronising decoder), then the slice
+        size_t n = 0;
+        const Status q = wdecompress_host(ctx, cd, nullptr, 0, &n);
+        if (q.code != HUFF_OK && q.code != HUFF_E_BUFFER_TOO_SMALL) return q;
+        if (!range_inside(first, count, n)) return Status::err(HUFF_E_INVALID_ARG, "letter range outside the stream");
+        if (cap_letters < count) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+        if (count == 0) return Status::ok();
+        std::vector<uint8_t> all(n * W);
+        HUFF_TRY(wdecompress_host(ctx, cd, all.data(), n, &n));
+        std::memcpy(out, all.data() + first * W, count * W);
+        return Status::ok();
+    }
+    const uint64_t n = cd->index->n;
+    if (!range_inside(first, count, n)) return Status::err(HUFF_E_INVALID_ARG, "letter range outside the stream");
+    if (cap_letters < count) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+    if (count == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    hipStream_t s = ctx->stream;
+    HUFF_TRY(ctx->d_in.ensure(cd->comp.size() + 16));
+    HIP_TRY(hipMemcpyAsync(ctx->d_in.p, cd->comp.data(), cd->comp.size(), hipMemcpyHostToDevice, s));
+    HUFF_TRY(ctx->d_out.ensure(count * W + 16));
+    huff_wenc e;
+    HUFF_TRY(e.init(ctx, W, nullptr, n));
+    HUFF_TRY(e.upload_index(*cd->index));
+    const uint64_t zero = 0;
+    uint32_t st = 0;
+    HUFF_TRY(e.decode_ranges(cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(), &first, &count,
+                             &zero, 1, static_cast<uint8_t*>(ctx->d_out.p), count, &st));
+    if (st != HUFF_OK) return Status::err(static_cast<int>(st), "the stream does not decode along its restart index");
+    HIP_TRY(hipMemcpyAsync(out, ctx->d_out.p, count * W, hipMemcpyDeviceToHost, s));
     return ctx->sync();
 }
 

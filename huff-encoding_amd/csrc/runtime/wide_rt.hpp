@@ -49,6 +49,8 @@ struct huff_wenc {
     const huff::WideDecTables* dt = nullptr;
     uint64_t bits_tree = 0;  // tree of the last pass A (0: none)
     uint64_t total_bits = 0;
+    bool index_uploaded = false;  // the index is upload_index's (of whatever tree), not a pass A's
+    DevBuf range_req, range_status;
 
     huff::Status init(huff_ctx* c, uint32_t w, const uint8_t* d, uint64_t nletters);
     huff::dev::WideArgs enc_args(bool pack_pass) const;  // the table and job fields of a pass
@@ -57,6 +59,11 @@ struct huff_wenc {
     huff::Status pack(const huff_wtree* t, uint8_t* d_out, size_t out_cap, uint64_t* total);
     huff::Status decode(const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes, uint8_t* d_out,
                         const uint64_t* sub_abs = nullptr, bool skip_packed = false);
+    // letter ranges through the restart index as it stands (huff_wenc_decode_ranges,
+    // wdecode_ranges.hip); first, count, out_begin (letters) and status are host arrays
+    huff::Status decode_ranges(const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes, const uint64_t* first,
+                               const uint64_t* count, const uint64_t* out_begin, uint32_t nreq, uint8_t* d_out,
+                               size_t out_cap_letters, uint32_t* status);
     huff::Status upload_dec(const huff_wtree* t);
     huff::Status download_index(huff_index_host& idx);
     huff::Status upload_index(const huff_index_host& idx);
@@ -69,6 +76,8 @@ Status wcompress_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, siz
                       huff_wcompress_data** out, u128* missing);
 Status wdecompress_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint8_t* out, size_t cap_letters,
                         size_t* n_out);
+Status wdecompress_range_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count,
+                              uint8_t* out, size_t cap_letters);
 // index-free decode of a device stream; d_out == nullptr: count only
 Status wdecode_indexless_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes,
                              uint64_t valid_bits, uint8_t* d_out, size_t cap_letters, uint64_t* n_out);

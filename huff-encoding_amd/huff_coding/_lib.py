@@ -181,6 +181,11 @@ SIGNATURES = [
     ("huff_diag_wide_index_form_name", C.c_char_p, [C.c_uint32]),
     ("huff_diag_wide_index_form_launches", C.c_uint64, [C.c_uint32]),
     ("huff_wtree_diag", i, [vp, u64p]),
+    ("huff_wenc_decode_ranges", i, [vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, sz, vp]),
+    ("huff_wdecompress_range", i, [vp, vp, C.c_uint64, C.c_uint64, vp, sz]),
+    ("huff_diag_wrange_builds", C.c_uint32, []),
+    ("huff_diag_wrange_build_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_wrange_build_launches", C.c_uint64, [C.c_uint32]),
 ]
 
 _lib = None
@@ -236,6 +241,14 @@ def wide_index_form_launches() -> dict:
     L = load()
     return {L.huff_diag_wide_index_form_name(k).decode(): L.huff_diag_wide_index_form_launches(k)
             for k in range(L.huff_diag_wide_index_forms())}
+
+
+def wrange_build_launches() -> dict:
+    """{build name: launches so far} of the wide range kernel's compiled builds
+    (huff_diag_wrange_build_*), process-wide, in the launcher's order"""
+    L = load()
+    return {L.huff_diag_wrange_build_name(k).decode(): L.huff_diag_wrange_build_launches(k)
+            for k in range(L.huff_diag_wrange_builds())}
 
 
 def last_error() -> str:

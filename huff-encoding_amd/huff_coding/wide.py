@@ -336,6 +336,21 @@ def decompress(comp_data: WideCompressData, ctx=None) -> np.ndarray:
     return out[: n.value]
 
 
+def decompress_range(comp_data: WideCompressData, first: int, count: int, ctx=None) -> np.ndarray:
+    """the letters [first, first + count) of comp_data (huff_wdecompress_range):
+    data from compress / compress_with_tree carries a restart index and only
+    the blocks of the range are decoded; data from try_from_bytes / new has
+    none and is decoded whole, then sliced (the slow route)"""
+    lt = comp_data.ltype
+    if first < 0 or first >= 1 << 64 or count < 0 or count >= 1 << 44:  # a job holds fewer than 2^44 letters
+        from . import HuffError
+
+        raise HuffError(_lib.E_INVALID_ARG, "letter range outside the stream")
+    out = np.empty(max(count, 1), lt.np)
+    _check(load().huff_wdecompress_range(_ctx(ctx).h, comp_data.h, first, count, out.ctypes.data, count))
+    return out[:count]
+
+
 class WideEncodeJob:
     """device-resident job over letters in HBM (huff_wenc_*)"""
 
@@ -369,6 +384,35 @@ class WideEncodeJob:
 
     def decode(self, tree: WideTree, d_comp: int, d_out: int):
         _check(load().huff_wenc_decode(self.h, tree.h, C.c_void_p(d_comp), C.c_void_p(d_out)))
+
+    def decode_ranges(self, tree: WideTree, d_comp: int, comp_bytes: int, first, count, d_out: int, out_cap: int,
+                      out_begin=None) -> np.ndarray:
+        """random access into this job's pack output (huff_wenc_decode_ranges):
+        the letters [first[r], first[r] + count[r]) land at d_out +
+        out_begin[r] * width; only the 64-letter blocks they touch are
+        decoded. first, count, out_begin and out_cap are in letters.
+        out_begin=None lays the requests out tightly in request order. Returns
+        the requests' statuses (uint32: 0, E_INVALID_ARG for a range outside
+        the job or a slot outside out_cap, E_CORRUPT)."""
+        f = np.ascontiguousarray(first, np.uint64).reshape(-1)
+        c = np.ascontiguousarray(count, np.uint64).reshape(-1)
+        if f.size != c.size:
+            raise ValueError("first and count differ in length")
+        if out_begin is None:
+            ob = np.zeros(f.size, np.uint64)
+            pos = 0  # Python sums: a count near 2^64 must not wrap a position back into the buffer
+            for r, m in enumerate(c.tolist()):
+                ob[r] = min(pos, 0xFFFFFFFFFFFFFFFF)
+                pos += m
+        else:
+            ob = np.ascontiguousarray(out_begin, np.uint64).reshape(-1)
+            if ob.size != f.size:
+                raise ValueError("first and out_begin differ in length")
+        st = np.zeros(f.size, np.uint32)
+        _check(load().huff_wenc_decode_ranges(self.h, tree.h, C.c_void_p(d_comp), comp_bytes, f.ctypes.data,
+                                              c.ctypes.data, ob.ctypes.data, f.size,
+                                              C.c_void_p(d_out) if d_out else None, out_cap, st.ctypes.data))
+        return st
 
 
 def decompress_dev(ctx, tree: WideTree, d_comp: int, comp_bytes: int, padding: int, d_out: int,

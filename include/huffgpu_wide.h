@@ -106,6 +106,45 @@ int huff_wenc_pack(huff_wenc* e, const huff_wtree* t, uint8_t* d_out, size_t out
  * d_comp at any alignment (a stream not 16-B aligned is first copied to an
  * aligned buffer of the context) */
 int huff_wenc_decode(huff_wenc* e, const huff_wtree* t, const uint8_t* d_comp, uint8_t* d_out);
+/* Random access into this job's pack output: request r gets the letters
+ * [first[r], first[r] + count[r]) of the job's n, stored at d_out +
+ * out_begin[r] * width; only the 64-letter blocks a request touches are
+ * decoded, each from its restart point. first, count, out_begin and
+ * out_cap_letters are in letters; first, count, out_begin and status are host
+ * arrays of nreq entries. status[r]: HUFF_OK; HUFF_E_INVALID_ARG when the
+ * range is not inside [0, n] or its slot [out_begin, out_begin + count) not
+ * inside out_cap_letters (such a request is not launched); HUFF_E_CORRUPT when
+ * the stream does not decode along the index on a block of the request (its
+ * slot may then hold anything; nothing outside it is written). count = 0 is
+ * HUFF_OK with no work; a call in which no request has letters launches
+ * nothing. Requests may overlap in the stream, not in d_out.
+ * The call itself fails, before any device work, with HUFF_E_INVALID_ARG for
+ * a null pointer, a d_comp that is not 4-byte aligned (unlike
+ * huff_wenc_decode the stream is never copied: that would cost what the call
+ * saves), a d_out not aligned to min(width, 16) bytes or a tree of another
+ * letter width, and with HUFF_E_STATE when the job has no restart index (no
+ * pass A has run) or its pass A was made with a tree other than t. comp_bytes
+ * = the readable bytes of d_comp (ceil(bits / 8) of the pack). The job is left
+ * as it was: a huff_wenc_decode after it behaves as without it.
+ * Cost: a touched block is decoded whole, one lane per block, so the call
+ * pays per block where huff_wenc_decode streams. Measured on an MI355X on
+ * 1 GiB streams ("Letter ranges"): 1,000 ranges of 256 letters
+ * cost 0.13-0.15 of a full decode; huff_wenc_decode is the faster call once
+ * the ranges add up to more than about a seventh of the stream (0.14 of it for
+ * 2-byte letters, 0.16 for 4-byte letters). */
+int huff_wenc_decode_ranges(huff_wenc* e, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                            const uint64_t* first, const uint64_t* count, const uint64_t* out_begin,
+                            uint32_t nreq, void* d_out, size_t out_cap_letters, uint32_t* status);
+/* The letters [first, first + count) of cd into out (cap_letters >= count).
+ * With a restart index (data of huff_wcompress / huff_wcompress_with_tree)
+ * only the blocks of the range are decoded (huff_wenc_decode_ranges); without
+ * one (huff_wcd_new, huff_wcd_try_from_bytes) the stream is decoded whole by
+ * the self-synchronising decoder and sliced: the slow route, which costs a
+ * huff_wdecompress. HUFF_E_INVALID_ARG: the range is not inside the stream's
+ * letters; HUFF_E_BUFFER_TOO_SMALL: cap_letters < count; HUFF_E_CORRUPT: the
+ * stream does not decode along its index. */
+int huff_wdecompress_range(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count,
+                           void* out, size_t cap_letters);
 /* self-synchronising decode of a device stream (no index), d_comp at any
  * alignment (as huff_wenc_decode): returns the count in *n_out; d_out NULL =
  * count only */
@@ -128,6 +167,14 @@ uint64_t huff_diag_wide_build_launches(uint32_t i);
 uint32_t huff_diag_wide_index_forms(void);
 const char* huff_diag_wide_index_form_name(uint32_t i);
 uint64_t huff_diag_wide_index_form_launches(uint32_t i);
+/* huff_wenc_decode_ranges takes its kernel from a table of its own: 9
+ * k_wdecode_ranges rows, letter type (uint8_t, uint16_t, uint32_t, uint64_t,
+ * U128) x leaf letters in LDS (true) or in global memory (false: more than
+ * 32 KiB of them), without the <uint8_t, false> row no tree can reach (256
+ * byte values always fit). Names and counts as above. */
+uint32_t huff_diag_wrange_builds(void);
+const char* huff_diag_wrange_build_name(uint32_t i);
+uint64_t huff_diag_wrange_build_launches(uint32_t i);
 /* The geometry of a tree's device tables, computed on the host (no context,
  * no GPU): the facts the launchers select a build by, not the build.
  * out[0] letter width in bytes          out[8]  deepest code (decoder tables)
