@@ -357,6 +357,24 @@ uint8_t huff_cd_padding(const huff_compress_data* cd) { return cd ? cd->padding 
 const huff_tree* huff_cd_tree(const huff_compress_data* cd) { return cd ? cd->tree : nullptr; }
 int huff_cd_has_index(const huff_compress_data* cd) { return cd && cd->index ? 1 : 0; }
 
+int huff_cd_build_index(huff_ctx* ctx, huff_compress_data* cd, uint64_t* n_out) {
+    if (!ctx || !cd || !n_out) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::build_index_host(ctx, cd, n_out); });
+}
+
+int huff_cd_index_view(const huff_compress_data* cd, uint64_t* n, const uint64_t** chunk_start, size_t* nchunk_entries,
+                       const uint32_t** sub_bit, size_t* nsub) {
+    if (!cd || !n || !chunk_start || !nchunk_entries || !sub_bit || !nsub)
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (!cd->index) return fail(HUFF_E_STATE, "the data carries no restart index (huff_cd_build_index)");
+    *n = cd->index->n;
+    *chunk_start = cd->index->chunk_start.data();
+    *nchunk_entries = cd->index->chunk_start.size();
+    *sub_bit = cd->index->sub_bit.data();
+    *nsub = cd->index->sub_bit.size();
+    return HUFF_OK;
+}
+
 int huff_cd_to_bytes(const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
     if (!cd || !out_len) return fail(HUFF_E_INVALID_ARG, "null argument");
     return guarded([&] {
@@ -413,6 +431,22 @@ int huff_enc_create(huff_ctx* ctx, const uint8_t* d_in, size_t n, huff_enc** out
     });
 }
 
+int huff_enc_from_stream(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, size_t comp_bytes, uint8_t padding,
+                         huff_enc** out, uint64_t* n_out) {
+    if (!ctx || !t || !out || !n_out || (!d_comp && comp_bytes)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    *out = nullptr;
+    *n_out = 0;
+    if (comp_bytes == 0) return fail(HUFF_E_EMPTY_COMP, "provided comp_bytes are empty");
+    if (padding > 7) return fail(HUFF_E_PADDING, "padding bits cannot be larger than 7");
+    return guarded([&] {
+        auto e = std::make_unique<huff_enc>();
+        HUFF_TRY(huff::build_index_dev(ctx, t, d_comp, comp_bytes, static_cast<uint64_t>(comp_bytes) * 8 - padding, *e));
+        *n_out = e->n;
+        *out = e.release();
+        return huff::Status::ok();
+    });
+}
+
 void huff_enc_free(huff_enc* e) {
     if (!e) return;
     if (e->ctx) {
@@ -462,6 +496,7 @@ int huff_enc_pack_shards(huff_enc* e, const uint64_t* hists, uint32_t world, uin
     if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(HUFF_E_INVALID_ARG, "d_out must be 16-byte aligned");
     *tree_out = nullptr;
     return guarded([&]() -> huff::Status {
+        HUFF_TRY(e->encode_guard());
         if (!e->have_hist) {  // pass 1 ran as huff_enc_hist_row: this shard's row is hists[rank]
             std::memcpy(e->w, hists + static_cast<size_t>(rank) * 256, sizeof(e->w));
             e->have_hist = true;

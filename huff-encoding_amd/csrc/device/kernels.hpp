@@ -709,6 +709,38 @@ constexpr uint64_t kSkipPosMask = (1ull << 48) - 1;
 hipError_t launch_indexless_mark(const IndexlessArgs& a, const uint64_t* off, uint64_t* sub_abs, uint32_t shift,
                                  hipStream_t s);
 bool indexless_staged(const IndexlessArgs& a);  // k_spec/k_mark LDS variants apply
+// The restart index of a settled stream (index_build.hip; host/index_plan.hpp).
+// k_index_long: the walked marks (sub_abs64[j] = the first bit of letter kIdx j,
+// as k_mark_lds writes them) from the unstaged pass's segments: lane i walks
+// the c[i] codes of segment i from s[i]; off = the exclusive scan of c.
+struct IndexLongArgs {
+    const uint8_t* comp;          // 4-B aligned
+    uint64_t comp_bytes;
+    uint64_t valid_bits;
+    const uint32_t* lut;          // DecodeArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint64_t* s;            // [nseg]
+    const uint64_t* c;            // [nseg]
+    const uint64_t* off;          // [nseg]
+    uint64_t nseg;
+    uint64_t total;               // the stream's letters: only slots below ceil(total / kIdx) are written
+    uint64_t* sub_abs64;
+};
+// k_index_pack: the marks of n >= 1 letters and the stream's end bit (*end,
+// k_walk_end's output) as chunk_start[ceil(n / kChunk) + 1] and
+// sub_bit[ceil(n / kIdx)]; *flag (zeroed) gets the kIndexBad* bits of what the
+// marks fail (index_mark_flags)
+struct IndexPackArgs {
+    const uint64_t* sub_abs64;
+    const unsigned long long* end;
+    uint64_t n;
+    uint64_t valid_bits;
+    uint64_t* chunk_start;
+    uint32_t* sub_bit;
+    unsigned int* flag;
+};
+hipError_t launch_index_long(const IndexLongArgs& a, hipStream_t s);
+hipError_t launch_index_pack(const IndexPackArgs& a, hipStream_t s);
 hipError_t launch_bytemap(const BytemapArgs& a, hipStream_t s);
 // letter checksums of the decode check build (checksum.hip): per task of
 // kTaskSym letters, sum and position-weighted sum (u64 = s2 << 32 | s1);

@@ -17,6 +17,18 @@ Status decode_indexless_dev(huff_ctx* ctx, const uint8_t* d_comp, uint64_t comp_
 Status decode_indexless_host(huff_ctx* ctx, const uint8_t* comp, size_t len, uint64_t valid_bits,
                              const huff_tree* t, std::vector<uint8_t>& out);
 
+// The restart index of a stream that came without one, built on the device
+// into the fresh job e (huff_enc_from_stream): the restart-point step with
+// walked marks (k_index_long's for the unstaged pass), k_walk_end from the last
+// mark, k_index_pack. e becomes a decode-only job of the stream's letters
+// (e.n), its index in the encoder's chunk_start + sub_bit form; an all-8-bit
+// tree gets the job's pending arithmetic index. HUFF_E_CODE_TOO_LONG past
+// kLongMaxLen bits, HUFF_E_CORRUPT when k_index_pack refuses the marks.
+Status build_index_dev(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, uint64_t comp_bytes,
+                       uint64_t valid_bits, huff_enc& e);
+// huff_cd_build_index: the stream staged, build_index_dev, the index downloaded into cd
+Status build_index_host(huff_ctx* ctx, huff_compress_data* cd, uint64_t* n_out);
+
 // The restart marks a decoder of the settled stream takes, one per 64 letters.
 enum class MarkForm {
     Compact,  // mark32 (u32 per mark) + task_seg (u32 per task): k_decode_fixed's skip build (dev::mark32_*)
@@ -49,6 +61,7 @@ struct IndexlessStep {
     DevBuf s, x0, c, off, flag, tsum, samp, tm, dl, fixlist, chain, rec;
     DevBuf wtot, woff;  // per-workgroup code counts of the staged pass and their exclusive scan
     DevBuf sub_abs, m32, tseg;  // the marks (sub_abs also: the serial deep walk's count)
+    DevBuf built;  // build_index_dev: the stream's end bit (u64) and k_index_pack's flag word
 
 private:
     MarkForm form_ = MarkForm::Compact;

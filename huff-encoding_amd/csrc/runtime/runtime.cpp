@@ -448,7 +448,14 @@ static huff::Status pending_guard(const huff_ctx* ctx, const huff_enc* e) {
     return huff::Status::ok();
 }
 
+huff::Status huff_enc::encode_guard() const {
+    if (decode_only)
+        return huff::Status::err(HUFF_E_STATE, "a job over a foreign stream (huff_enc_from_stream) only decodes");
+    return huff::Status::ok();
+}
+
 huff::Status huff_enc::hist_launch() {
+    HUFF_TRY(encode_guard());
     HUFF_TRY(ctx->activate());
     HUFF_TRY(pending_guard(ctx, this));
     if (nchunks == 0 || ctx->hist_pending == this) return huff::Status::ok();
@@ -460,6 +467,7 @@ huff::Status huff_enc::hist_launch() {
 }
 
 huff::Status huff_enc::hist() {
+    HUFF_TRY(encode_guard());
     HUFF_TRY(ctx->activate());
     HUFF_TRY(pending_guard(ctx, this));
     if (nchunks == 0) {
@@ -482,6 +490,7 @@ huff::Status huff_enc::hist() {
 }
 
 huff::Status huff_enc::hist_known(const uint64_t counts[256]) {
+    HUFF_TRY(encode_guard());
     HUFF_TRY(ctx->activate());
     if (ctx->hist_pending == this) ctx->hist_pending = nullptr;  // its weights are not wanted now
     std::memcpy(w, counts, sizeof w);
@@ -495,6 +504,7 @@ huff::Status huff_enc::hist_known(const uint64_t counts[256]) {
 }
 
 huff::Status huff_enc::hist_row(long long* d_row) {
+    HUFF_TRY(encode_guard());
     HUFF_TRY(ctx->activate());
     if (ctx->hist_pending == this) ctx->hist_pending = nullptr;
     hipStream_t s = ctx->stream;
@@ -516,6 +526,7 @@ huff::Status huff_enc::hist_row(long long* d_row) {
 }
 
 huff::Status huff_enc::bits(const huff_tree* t, uint64_t* total) {
+    HUFF_TRY(encode_guard());
     if (!have_hist) return huff::Status::err(HUFF_E_STATE, "huff_enc_hist must run before bits/pack");
     const huff::EncTables& et = t->enc_tables();
     uint64_t b = 0;

@@ -214,6 +214,10 @@ struct huff_enc {
     huff::Status expand_index();
     uint64_t w[256] = {};
     bool have_hist = false;
+    // a job over a foreign stream (huff_enc_from_stream): it has no input, and
+    // the encode calls answer HUFF_E_STATE before they touch a device
+    bool decode_only = false;
+    huff::Status encode_guard() const;
     // state of the last pack (for decode)
     bool packed = false;
     uint64_t packed_tree_id = 0;

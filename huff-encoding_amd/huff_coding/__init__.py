@@ -434,6 +434,30 @@ class CompressData:
     def has_index(self) -> bool:
         return bool(load().huff_cd_has_index(self.h))
 
+    def build_index(self, ctx: Optional["Context"] = None) -> int:
+        """the restart index of data that came without one (new, try_from_bytes),
+        built on the GPU and attached (huff_cd_build_index): decompress and
+        decompress_range then take their indexed routes. Returns the stream's
+        letter count; with an index already there, that index's, with no device
+        work. Trees with codes longer than 57 bits raise
+        HuffError(CODE_TOO_LONG) and leave the data as it was."""
+        ctx = ctx or default_context()
+        n = C.c_uint64()
+        _check(load().huff_cd_build_index(ctx.h, self.h, C.byref(n)))
+        return n.value
+
+    def index_view(self):
+        """(n, chunk_start, sub_bit) of the attached restart index, as numpy
+        copies (huff_cd_index_view): uint64 first bits of every 65,536-letter
+        chunk and the stream's end bit, uint32 offsets of every 64th letter from
+        its chunk's first bit. HuffError(STATE) without an index."""
+        n, nc, ns = C.c_uint64(), C.c_size_t(), C.c_size_t()
+        cs, sb = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
+        _check(load().huff_cd_index_view(self.h, C.byref(n), C.byref(cs), C.byref(nc), C.byref(sb), C.byref(ns)))
+        chunk_start = np.ctypeslib.as_array(cs, (nc.value,)).copy() if nc.value else np.zeros(0, np.uint64)
+        sub_bit = np.ctypeslib.as_array(sb, (ns.value,)).copy() if ns.value else np.zeros(0, np.uint32)
+        return n.value, chunk_start, sub_bit
+
     def to_bytes(self) -> bytes:
         """comp.rs:279-300"""
         n = C.c_size_t()
@@ -492,8 +516,8 @@ def decompress_range(comp_data: CompressData, first: int, count: int, ctx: Optio
     (huff_decompress_range): data from compress / compress_with_tree carries a
     restart index and decodes only the 64-letter blocks the range touches; data
     from try_from_bytes, or with codes longer than 57 bits, is decoded whole and
-    sliced (the slow route). A range outside the stream raises
-    HuffError(INVALID_ARG)."""
+    sliced (the slow route), until CompressData.build_index() has given it an
+    index. A range outside the stream raises HuffError(INVALID_ARG)."""
     ctx = ctx or default_context()
     if first < 0 or first >= 1 << 64 or count < 0 or count >= 1 << 48:  # a stream holds fewer than 2^48 letters
         raise HuffError(_lib.E_INVALID_ARG, "letter range outside the stream")

@@ -86,6 +86,8 @@ SIGNATURES = [
     ("huff_cd_padding", C.c_uint8, [vp]),
     ("huff_cd_tree", vp, [vp]),
     ("huff_cd_has_index", i, [vp]),
+    ("huff_cd_build_index", i, [vp, vp, u64p]),
+    ("huff_cd_index_view", i, [vp, u64p, C.POINTER(u64p), szp, C.POINTER(C.POINTER(C.c_uint32)), szp]),
     ("huff_cd_to_bytes", i, [vp, u8p, sz, szp]),
     ("huff_cd_try_from_bytes", i, [vp, sz, C.POINTER(vp)]),
     ("huff_compress_with_tree", i, [vp, vp, sz, vp, C.POINTER(vp)]),
@@ -93,6 +95,7 @@ SIGNATURES = [
     ("huff_decompress", i, [vp, vp, u8p, sz, szp]),
     ("huff_decompress_range", i, [vp, vp, C.c_uint64, C.c_uint64, u8p, sz]),
     ("huff_enc_create", i, [vp, vp, sz, C.POINTER(vp)]),
+    ("huff_enc_from_stream", i, [vp, vp, vp, sz, C.c_uint8, C.POINTER(vp), u64p]),
     ("huff_enc_free", None, [vp]),
     ("huff_enc_hist", i, [vp, vp]),
     ("huff_enc_hist_row", i, [vp, vp]),

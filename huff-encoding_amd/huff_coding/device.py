@@ -30,6 +30,23 @@ class EncodeJob:
         self.h = C.c_void_p()
         _check(load().huff_enc_create(ctx.h, C.c_void_p(d_in), n, C.byref(self.h)))
 
+    @classmethod
+    def from_stream(cls, ctx, tree, comp_ptr: int, comp_bytes: int, padding: int) -> "EncodeJob":
+        """a decode-only job over a foreign stream in HBM (huff_enc_from_stream):
+        comp_bytes bytes at comp_ptr (any alignment), the last with `padding`
+        pad bits. Its restart index is built on the device and stays there;
+        .n is the stream's letter count. decode() and decode_ranges() serve it
+        with the same tree; the encode calls raise HuffError(STATE)."""
+        job = cls.__new__(cls)
+        job.ctx = ctx
+        job.n = 0
+        job.h = C.c_void_p()
+        n = C.c_uint64()
+        _check(load().huff_enc_from_stream(ctx.h, tree.h, C.c_void_p(comp_ptr) if comp_ptr else None, comp_bytes,
+                                           padding, C.byref(job.h), C.byref(n)))
+        job.n = n.value
+        return job
+
     def close(self):
         if getattr(self, "h", None):
             load().huff_enc_free(self.h)

@@ -82,8 +82,9 @@ int huff_ctx_device(const huff_ctx* ctx);
  * launches is bracketed by HIP events on the context's stream. */
 int huff_ctx_set_timing(huff_ctx* ctx, int on);
 /* Sum of the timed durations (ms) and launch count of kernel `name`
- * ("hist", "chunk_bits", "scan", "pack", "decode", "indexless_*") since the
- * last reset; synchronises the stream. */
+ * ("hist", "chunk_bits", "scan", "pack", "decode", "decode_ranges",
+ * "index_long", "index_pack", "indexless_*") since the last reset;
+ * synchronises the stream. */
 int huff_ctx_kernel_time(huff_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
 int huff_ctx_reset_timing(huff_ctx* ctx);
 
@@ -167,6 +168,28 @@ uint8_t huff_cd_padding(const huff_compress_data* cd);
 const huff_tree* huff_cd_tree(const huff_compress_data* cd);
 /* whether the GPU restart index of the encoder is attached (decode fast path) */
 int huff_cd_has_index(const huff_compress_data* cd);
+/* The restart index of a CompressData that came without one (huff_cd_new,
+ * huff_cd_try_from_bytes; no reference counterpart): the stream is staged to
+ * the device, its index built there (the index-free decode's restart-point
+ * step, then a walk to every 64th letter; no letter is written) and
+ * downloaded into cd. Afterwards huff_cd_has_index is 1, and huff_decompress
+ * and huff_decompress_range take their indexed routes; the letters are those
+ * huff_decompress gave before, a trailing incomplete code dropped as the
+ * reference drops it. *n_out = the stream's letters (0 for a stream without
+ * one complete code). With an index already attached: HUFF_OK, *n_out = its
+ * letters, no device work. HUFF_E_CODE_TOO_LONG for a tree with a code longer
+ * than 57 bits (the range kernel cannot serve it either), HUFF_E_CORRUPT when
+ * the walked restart points are not in order; on any error cd is unchanged.
+ * Not thread-safe against concurrent readers of the same cd.
+ * Cost: DESIGN.md §12, "Building the index of a foreign stream". */
+int huff_cd_build_index(huff_ctx* ctx, huff_compress_data* cd, uint64_t* n_out);
+/* A read-only view of cd's restart index, valid as long as cd: *n letters,
+ * chunk_start[*nchunk_entries] (the
+ * first bit of every 65,536-letter chunk, then the stream's end bit) and
+ * sub_bit[*nsub] (the first bit of every 64th letter, from its chunk's).
+ * HUFF_E_STATE without an index. This is also how a caller persists one. */
+int huff_cd_index_view(const huff_compress_data* cd, uint64_t* n, const uint64_t** chunk_start,
+                       size_t* nchunk_entries, const uint32_t** sub_bit, size_t* nsub);
 /* CompressData::to_bytes (comp.rs:279-300) */
 int huff_cd_to_bytes(const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
 /* CompressData::try_from_bytes (comp.rs:128-184) */
@@ -191,7 +214,8 @@ int huff_decompress(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out, s
  * touched 64-letter blocks (huff_enc_decode_ranges' kernel; the whole stream
  * is still staged to the device). One without an index (huff_cd_new,
  * huff_cd_try_from_bytes) or with a deeper tree takes the slow route: it is
- * decoded whole and sliced. HUFF_E_INVALID_ARG: the range is not inside the
+ * decoded whole and sliced. A stream without an index leaves the slow route
+ * for good after one huff_cd_build_index. HUFF_E_INVALID_ARG: the range is not inside the
  * stream's letters; HUFF_E_BUFFER_TOO_SMALL: cap < count; HUFF_E_CORRUPT: the
  * stream does not decode along its index. */
 int huff_decompress_range(huff_ctx* ctx, const huff_compress_data* cd, uint64_t first, uint64_t count,
@@ -294,6 +318,25 @@ int huff_enc_decode(huff_enc* e, const huff_tree* t, const uint8_t* d_comp, uint
 int huff_enc_decode_ranges(huff_enc* e, const huff_tree* t, const uint8_t* d_comp, const uint64_t* first,
                            const uint64_t* count, const uint64_t* out_begin, uint32_t nreq, uint8_t* d_out,
                            size_t out_cap, uint32_t* status);
+
+/* A decode-only job over a foreign stream already in HBM (one written by the
+ * reference CPU path, huff_dev_decompress's input): comp_bytes bytes at d_comp,
+ * the last holding `padding` pad bits. d_comp may have any alignment for this
+ * call (a stream not 16-B aligned is first copied to an aligned buffer of the
+ * context). The stream's restart index is built on the device as
+ * huff_cd_build_index builds it and stays there; only the letter count, the
+ * end bit and a flag word come back. *n_out = the job's letters. The job
+ * remembers t's codes: huff_enc_decode and huff_enc_decode_ranges then serve
+ * the stream under their own rules (d_comp 4-byte aligned there; a tree of
+ * other codes is HUFF_E_STATE). The encode calls on such a job (hist,
+ * hist_launch, hist_row, bits, pack, pack_shards, compress) return
+ * HUFF_E_STATE and touch no device. HUFF_E_INVALID_ARG for a null pointer,
+ * HUFF_E_EMPTY_COMP / HUFF_E_PADDING as huff_cd_new, HUFF_E_CODE_TOO_LONG for
+ * a tree with a code longer than 57 bits, HUFF_E_CORRUPT when the walked
+ * restart points are not in order; *out is NULL on any error. Free with
+ * huff_enc_free. */
+int huff_enc_from_stream(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, size_t comp_bytes,
+                         uint8_t padding, huff_enc** out, uint64_t* n_out);
 
 /* ------------------------------------------------------------------------ */
 /* multi-GPU: sharded compress over an RCCL communicator  */
