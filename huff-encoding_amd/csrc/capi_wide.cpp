@@ -189,6 +189,24 @@ uint8_t huff_wcd_padding(const huff_wcompress_data* cd) { return cd ? cd->paddin
 const huff_wtree* huff_wcd_tree(const huff_wcompress_data* cd) { return cd ? cd->tree : nullptr; }
 int huff_wcd_has_index(const huff_wcompress_data* cd) { return cd && cd->index ? 1 : 0; }
 
+int huff_wcd_build_index(huff_ctx* ctx, huff_wcompress_data* cd, uint64_t* n_out) {
+    if (!ctx || !cd || !n_out) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::wbuild_index_host(ctx, cd, n_out); });
+}
+
+int huff_wcd_index_view(const huff_wcompress_data* cd, uint64_t* n, const uint64_t** chunk_start,
+                        size_t* nchunk_entries, const uint32_t** sub_bit, size_t* nsub) {
+    if (!cd || !n || !chunk_start || !nchunk_entries || !sub_bit || !nsub)
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (!cd->index) return fail(HUFF_E_STATE, "the data carries no restart index (huff_wcd_build_index)");
+    *n = cd->index->n;
+    *chunk_start = cd->index->chunk_start.data();
+    *nchunk_entries = cd->index->chunk_start.size();
+    *sub_bit = cd->index->sub_bit.data();
+    *nsub = cd->index->sub_bit.size();
+    return HUFF_OK;
+}
+
 int huff_wcd_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
     if (!cd || !out_len) return fail(HUFF_E_INVALID_ARG, "null argument");
     return guarded([&] {
@@ -264,6 +282,23 @@ int huff_wenc_create(huff_ctx* ctx, uint32_t width, const void* d_in, size_t n, 
     });
 }
 
+int huff_wenc_from_stream(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                          uint8_t padding, huff_wenc** out, uint64_t* n_out) {
+    if (!ctx || !t || !out || !n_out || (!d_comp && comp_bytes)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    *out = nullptr;
+    *n_out = 0;
+    if (comp_bytes == 0) return fail(HUFF_E_EMPTY_COMP, "provided comp_bytes are empty");
+    if (padding > 7) return fail(HUFF_E_PADDING, "padding bits cannot be larger than 7");
+    return guarded([&] {
+        auto e = std::make_unique<huff_wenc>();
+        HUFF_TRY(huff::wbuild_index_dev(ctx, t, d_comp, comp_bytes, static_cast<uint64_t>(comp_bytes) * 8 - padding,
+                                        *e));
+        *n_out = e->n;
+        *out = e.release();
+        return huff::Status::ok();
+    });
+}
+
 void huff_wenc_free(huff_wenc* e) {
     if (!e) return;
     if (e->ctx) hipSetDevice(e->ctx->device);
@@ -291,6 +326,11 @@ int huff_wenc_decode(huff_wenc* e, const huff_wtree* t, const uint8_t* d_comp, u
     if (!e || !t || !d_comp || !d_out) return fail(HUFF_E_INVALID_ARG, "null argument");
     return guarded([&] {
         if (e->bits_tree == 0) return huff::Status::err(HUFF_E_STATE, "decode needs the job's restart index (pack first)");
+        if (e->decode_only) {  // the index is that of the stream under the tree it was built with
+            if (e->bits_tree != t->id)
+                return huff::Status::err(HUFF_E_STATE, "decode tree differs from the tree the job's index was built with");
+            if (e->n == 0) return huff::Status::ok();
+        }
         return e->decode(t, d_comp, (e->total_bits + 7) / 8, d_out);
     });
 }

@@ -741,6 +741,20 @@ struct IndexPackArgs {
 };
 hipError_t launch_index_long(const IndexLongArgs& a, hipStream_t s);
 hipError_t launch_index_pack(const IndexPackArgs& a, hipStream_t s);
+// k_windex_pack (windex_build.hip; host/windex_plan.hpp): the same marks of
+// n >= 1 wide letters in the wide encoder's geometry, chunk_start[ceil(n /
+// kWideChunk) + 1] and sub_bit[ceil(n / kWideRun)]; *flag (zeroed) gets the
+// kWIndexBad* bits (windex_mark_flags)
+struct WIndexPackArgs {
+    const uint64_t* sub_abs64;
+    const unsigned long long* end;
+    uint64_t n;
+    uint64_t valid_bits;
+    uint64_t* chunk_start;
+    uint32_t* sub_bit;
+    unsigned int* flag;
+};
+hipError_t launch_windex_pack(const WIndexPackArgs& a, hipStream_t s);
 hipError_t launch_bytemap(const BytemapArgs& a, hipStream_t s);
 // letter checksums of the decode check build (checksum.hip): per task of
 // kTaskSym letters, sum and position-weighted sum (u64 = s2 << 32 | s1);

@@ -1,6 +1,7 @@
 // indexless_rt.cpp — decode without a restart index: the restart-point step
 // (IndexlessStep), the byte decode's routes over it, and the restart index
-// built from it for a stream that came without one (build_index_dev).
+// built from it for a stream that came without one (build_index_dev, and
+// wbuild_index_dev for wide letters).
 #include "indexless_rt.hpp"
 
 #include <cstdio>
@@ -9,6 +10,8 @@
 #include <string>
 
 #include "../host/index_plan.hpp"
+#include "../host/windex_plan.hpp"
+#include "wide_rt.hpp"
 
 #define HIP_TRY(expr) HIP_TRY_RT(expr)
 
@@ -413,6 +416,100 @@ Status build_index_host(huff_ctx* ctx, huff_compress_data* cd, uint64_t* n_out) 
     HIP_TRY(hipMemcpyAsync(ctx->d_in.p, cd->comp.data(), cd->comp.size(), hipMemcpyHostToDevice, ctx->stream));
     huff_enc e;
     HUFF_TRY(build_index_dev(ctx, cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(), valid, e));
+    auto idx = std::make_unique<huff_index_host>();
+    HUFF_TRY(e.download_index(*idx));
+    *n_out = idx->n;
+    cd->index = std::move(idx);  // only now: on any error cd is as it was
+    return Status::ok();
+}
+
+static_assert(kWIndexBlock == dev::kWideRun && kWIndexChunk == dev::kWideChunk,
+              "host/windex_plan.hpp mirrors kWideRun and kWideChunk");
+
+// build_index_dev for a wide tree: the step runs on the tree's shape (code
+// lengths only, also k_index_long's table), the pack is the wide geometry's.
+// No arithmetic index for an all-8-bit shape: that one is huff_enc's.
+Status wbuild_index_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes,
+                        uint64_t valid_bits, huff_wenc& e) {
+    if (t->t.max_depth() > kWideMaxEncodeLen)
+        return Status::err(HUFF_E_CODE_TOO_LONG, "a wide restart index needs codes of at most 56 bits");
+    HUFF_TRY(ctx->activate());
+    IndexlessStep& st = ctx->indexless_ws();
+    if (valid_bits) {
+        HUFF_TRY(st.open(ctx, t->shape_tree(), d_comp, comp_bytes, valid_bits));
+        HUFF_TRY(st.count(MarkForm::Walked, std::nullopt));
+    }
+    const uint64_t n = valid_bits ? st.total : 0;
+    HUFF_TRY(e.init(ctx, t->t.width(), nullptr, n));
+    e.decode_only = true;
+    hipStream_t strm = ctx->stream;
+    if (n == 0) {  // no complete code: chunk_start = {0}, and no kernel over the unwritten segment records
+        HIP_TRY(hipMemsetAsync(e.chunk_start.p, 0, 8, strm));
+        if (valid_bits) HIP_TRY(hipEventRecord(ctx->lut_free, strm));
+        HUFF_TRY(ctx->sync());
+        e.total_bits = 0;
+        e.bits_tree = t->id;
+        return Status::ok();
+    }
+    if (st.staged()) {
+        HUFF_TRY(st.marks());
+    } else {  // k_emit's segments: the marks by their own walk
+        HUFF_TRY(st.sub_abs.ensure(windex_marks(n) * 8 + 8));
+        st.sub_abs64 = static_cast<const uint64_t*>(st.sub_abs.p);
+        dev::IndexLongArgs l{};
+        l.comp = st.a.comp;
+        l.comp_bytes = st.a.comp_bytes;
+        l.valid_bits = valid_bits;
+        l.lut = st.a.lut;
+        l.lut_bits = st.a.lut_bits;
+        l.s = st.a.s;
+        l.c = st.a.c;
+        l.off = static_cast<const uint64_t*>(st.off.p);
+        l.nseg = st.a.nseg;
+        l.total = n;
+        l.sub_abs64 = static_cast<uint64_t*>(st.sub_abs.p);
+        HUFF_TRY(ctx->timed("index_long", [&] { return dev::launch_index_long(l, strm); }));
+    }
+    HUFF_TRY(st.built.ensure(16));
+    HIP_TRY(hipMemsetAsync(st.built.p, 0, 16, strm));
+    auto* d_end = static_cast<unsigned long long*>(st.built.p);
+    const uint64_t m = ((n - 1) >> 6) << 6;  // the last mark: letter m
+    DevBuf none;
+    HUFF_TRY(walk_end(st, Target{none, nullptr, 0, d_end}, st.sub_abs64 + (m >> 6), 0, nullptr, n - m));
+    dev::WIndexPackArgs p{};
+    p.sub_abs64 = st.sub_abs64;
+    p.end = d_end;
+    p.n = n;
+    p.valid_bits = valid_bits;
+    p.chunk_start = static_cast<uint64_t*>(e.chunk_start.p);
+    p.sub_bit = static_cast<uint32_t*>(e.sub_bit.p);
+    p.flag = reinterpret_cast<unsigned int*>(d_end + 1);
+    HUFF_TRY(ctx->timed("windex_pack", [&] { return dev::launch_windex_pack(p, strm); }));
+    HIP_TRY(hipEventRecord(ctx->lut_free, strm));
+    uint64_t got[2] = {};  // the end bit and the flag word: the index itself stays on the device
+    HIP_TRY(hipMemcpyAsync(got, st.built.p, 16, hipMemcpyDeviceToHost, strm));
+    HUFF_TRY(ctx->sync());
+    if (got[1] & 0xFFFFFFFFull)
+        return Status::err(HUFF_E_CORRUPT, "the stream's restart marks are not in order (k_windex_pack flags " +
+                                               std::to_string(got[1] & 0xFFFFFFFFull) + ")");
+    e.total_bits = got[0];
+    e.bits_tree = t->id;
+    return Status::ok();
+}
+
+Status wbuild_index_host(huff_ctx* ctx, huff_wcompress_data* cd, uint64_t* n_out) {
+    if (cd->index) {
+        *n_out = cd->index->n;
+        return Status::ok();
+    }
+    if (cd->tree->t.max_depth() > kWideMaxEncodeLen)  // before the stream is staged
+        return Status::err(HUFF_E_CODE_TOO_LONG, "a wide restart index needs codes of at most 56 bits");
+    const uint64_t valid = static_cast<uint64_t>(cd->comp.size()) * 8 - cd->padding;
+    HUFF_TRY(ctx->activate());
+    HUFF_TRY(ctx->d_in.ensure(cd->comp.size() + 16));
+    HIP_TRY(hipMemcpyAsync(ctx->d_in.p, cd->comp.data(), cd->comp.size(), hipMemcpyHostToDevice, ctx->stream));
+    huff_wenc e;
+    HUFF_TRY(wbuild_index_dev(ctx, cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(), valid, e));
     auto idx = std::make_unique<huff_index_host>();
     HUFF_TRY(e.download_index(*idx));
     *n_out = idx->n;

@@ -98,6 +98,8 @@ huff::dev::WideArgs huff_wenc::enc_args(bool pack_pass) const {
 }
 
 Status huff_wenc::bits(const huff_wtree* t, uint64_t* total, huff::u128* missing_letter) {
+    if (decode_only)
+        return Status::err(HUFF_E_STATE, "a job over a foreign stream (huff_wenc_from_stream) only decodes");
     HUFF_TRY(ctx->activate());
     HUFF_TRY(t->enc_tables(&et));
     if (et->width != width) return Status::err(HUFF_E_INVALID_ARG, "the tree's letter width differs from the job's");
@@ -136,6 +138,8 @@ Status huff_wenc::bits(const huff_wtree* t, uint64_t* total, huff::u128* missing
 }
 
 Status huff_wenc::pack(const huff_wtree* t, uint8_t* d_out, size_t out_cap, uint64_t* total) {
+    if (decode_only)  // before the pass A below: there are no letters to read
+        return Status::err(HUFF_E_STATE, "a job over a foreign stream (huff_wenc_from_stream) only decodes");
     if (bits_tree != t->id) HUFF_TRY(bits(t, nullptr, nullptr));
     if (total) *total = total_bits;
     const uint64_t need = (total_bits + 7) / 8;

@@ -50,6 +50,9 @@ struct huff_wenc {
     uint64_t bits_tree = 0;  // tree of the last pass A (0: none)
     uint64_t total_bits = 0;
     bool index_uploaded = false;  // the index is upload_index's (of whatever tree), not a pass A's
+    // a job over a foreign stream (huff_wenc_from_stream): it has no input, and
+    // the encode passes answer HUFF_E_STATE before any launch
+    bool decode_only = false;
     DevBuf range_req, range_status;
 
     huff::Status init(huff_ctx* c, uint32_t w, const uint8_t* d, uint64_t nletters);
@@ -81,4 +84,15 @@ Status wdecompress_range_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint
 // index-free decode of a device stream; d_out == nullptr: count only
 Status wdecode_indexless_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes,
                              uint64_t valid_bits, uint8_t* d_out, size_t cap_letters, uint64_t* n_out);
+// The restart index of a wide stream that came without one, built on the
+// device into the fresh job e (huff_wenc_from_stream; indexless_rt.cpp): the
+// restart-point step on the tree's shape with walked marks (k_index_long's
+// past 32 bits), k_walk_end from the last mark, k_windex_pack. e becomes a
+// decode-only job of the stream's letters (e.n) with bits_tree = t->id and
+// total_bits = the end bit. HUFF_E_CODE_TOO_LONG past kWideMaxEncodeLen bits,
+// HUFF_E_CORRUPT when k_windex_pack refuses the marks.
+Status wbuild_index_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes,
+                        uint64_t valid_bits, huff_wenc& e);
+// huff_wcd_build_index: the stream staged, wbuild_index_dev, the index downloaded into cd
+Status wbuild_index_host(huff_ctx* ctx, huff_wcompress_data* cd, uint64_t* n_out);
 }  // namespace huff

@@ -189,6 +189,9 @@ SIGNATURES = [
     ("huff_diag_wrange_builds", C.c_uint32, []),
     ("huff_diag_wrange_build_name", C.c_char_p, [C.c_uint32]),
     ("huff_diag_wrange_build_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_wcd_build_index", i, [vp, vp, u64p]),
+    ("huff_wcd_index_view", i, [vp, u64p, C.POINTER(u64p), szp, C.POINTER(C.POINTER(C.c_uint32)), szp]),
+    ("huff_wenc_from_stream", i, [vp, vp, vp, sz, C.c_uint8, C.POINTER(vp), u64p]),
 ]
 
 _lib = None

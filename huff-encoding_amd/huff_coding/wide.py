@@ -263,6 +263,30 @@ class WideCompressData:
     def has_index(self) -> bool:
         return bool(load().huff_wcd_has_index(self.h))
 
+    def build_index(self, ctx=None) -> int:
+        """the restart index of data that came without one (new, try_from_bytes),
+        built on the GPU and attached (huff_wcd_build_index): decompress and
+        decompress_range then take their indexed routes, also for trees with
+        codes of 33-56 bits, which decompress refuses without an index. Returns
+        the stream's letter count; with an index already there, that index's,
+        with no device work. Trees with codes longer than 56 bits raise
+        HuffError(CODE_TOO_LONG) and leave the data as it was."""
+        n = C.c_uint64()
+        _check(load().huff_wcd_build_index(_ctx(ctx).h, self.h, C.byref(n)))
+        return n.value
+
+    def index_view(self):
+        """(n, chunk_start, sub_bit) of the attached restart index, as numpy
+        copies (huff_wcd_index_view): uint64 first bits of every 16,384-letter
+        chunk and the stream's end bit, uint32 offsets of every 64th letter from
+        its chunk's first bit. HuffError(STATE) without an index."""
+        n, nc, ns = C.c_uint64(), C.c_size_t(), C.c_size_t()
+        cs, sb = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
+        _check(load().huff_wcd_index_view(self.h, C.byref(n), C.byref(cs), C.byref(nc), C.byref(sb), C.byref(ns)))
+        chunk_start = np.ctypeslib.as_array(cs, (nc.value,)).copy() if nc.value else np.zeros(0, np.uint64)
+        sub_bit = np.ctypeslib.as_array(sb, (ns.value,)).copy() if ns.value else np.zeros(0, np.uint32)
+        return n.value, chunk_start, sub_bit
+
     def to_bytes(self) -> bytes:
         n = C.c_size_t()
         rc = load().huff_wcd_to_bytes(self.h, None, 0, C.byref(n))
@@ -340,7 +364,8 @@ def decompress_range(comp_data: WideCompressData, first: int, count: int, ctx=No
     """the letters [first, first + count) of comp_data (huff_wdecompress_range):
     data from compress / compress_with_tree carries a restart index and only
     the blocks of the range are decoded; data from try_from_bytes / new has
-    none and is decoded whole, then sliced (the slow route)"""
+    none and is decoded whole, then sliced (the slow route), until
+    WideCompressData.build_index() has given it an index"""
     lt = comp_data.ltype
     if first < 0 or first >= 1 << 64 or count < 0 or count >= 1 << 44:  # a job holds fewer than 2^44 letters
         from . import HuffError
@@ -360,6 +385,26 @@ class WideEncodeJob:
         self.width = width
         self.h = C.c_void_p()
         _check(load().huff_wenc_create(ctx.h, width, C.c_void_p(d_in), n, C.byref(self.h)))
+
+    @classmethod
+    def from_stream(cls, ctx, tree: WideTree, comp_ptr: int, comp_bytes: int, padding: int) -> "WideEncodeJob":
+        """a decode-only job over a foreign stream in HBM (huff_wenc_from_stream):
+        comp_bytes bytes at comp_ptr (any alignment), the last with `padding`
+        pad bits. Its restart index is built on the device and stays there;
+        .n is the stream's letter count, .width the tree's. decode() and
+        decode_ranges() serve it with the same tree (kept alive as .tree);
+        bits() and pack() raise HuffError(STATE)."""
+        job = cls.__new__(cls)
+        job.ctx = ctx
+        job.tree = tree
+        job.n = 0
+        job.width = tree.ltype.width
+        job.h = C.c_void_p()
+        n = C.c_uint64()
+        _check(load().huff_wenc_from_stream(ctx.h, tree.h, C.c_void_p(comp_ptr) if comp_ptr else None, comp_bytes,
+                                            padding, C.byref(job.h), C.byref(n)))
+        job.n = n.value
+        return job
 
     def close(self):
         if getattr(self, "h", None):

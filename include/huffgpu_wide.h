@@ -74,6 +74,31 @@ int huff_wcd_comp_bytes(const huff_wcompress_data* cd, const uint8_t** ptr, size
 uint8_t huff_wcd_padding(const huff_wcompress_data* cd);
 const huff_wtree* huff_wcd_tree(const huff_wcompress_data* cd);
 int huff_wcd_has_index(const huff_wcompress_data* cd);
+/* The restart index of a CompressData<L> that came without one (huff_wcd_new,
+ * huff_wcd_try_from_bytes; no reference counterpart), as huff_cd_build_index
+ * for bytes: the stream is staged to the device, its index built there (the
+ * index-free decode's restart-point step on the tree's shape, then a walk to
+ * every 64th letter; no letter is written) and downloaded into cd. Afterwards
+ * huff_wcd_has_index is 1, huff_wdecompress takes the indexed route and
+ * huff_wdecompress_range decodes only the touched blocks, also for trees with
+ * codes of 33-56 bits, which huff_wdecompress refuses without an index. The
+ * letters are those of the index-free decode, a trailing incomplete code
+ * dropped. *n_out = the stream's letters (0 for a stream without one complete
+ * code). With an index already attached: HUFF_OK, *n_out = its letters, no
+ * device work. HUFF_E_CODE_TOO_LONG for a tree with a code longer than 56 bits
+ * (the wide encoder's limit), HUFF_E_CORRUPT when the walked restart points
+ * are not in order; on any error cd is unchanged. Not thread-safe against
+ * concurrent readers of the same cd.
+ * Cost: DESIGN.md §9, "Index build". */
+int huff_wcd_build_index(huff_ctx* ctx, huff_wcompress_data* cd, uint64_t* n_out);
+/* A read-only view of cd's restart index, valid until cd is freed: *n letters,
+ * chunk_start[*nchunk_entries] (the first bit of every 16,384-letter chunk,
+ * then the stream's end bit: ceil(n / 16384) + 1 entries) and sub_bit[*nsub]
+ * (the first bit of every 64th letter, from its chunk's: ceil(n / 64)
+ * entries). HUFF_E_STATE without an index; data of huff_wcompress /
+ * huff_wcompress_with_tree shows the encoder's. */
+int huff_wcd_index_view(const huff_wcompress_data* cd, uint64_t* n, const uint64_t** chunk_start,
+                        size_t* nchunk_entries, const uint32_t** sub_bit, size_t* nsub);
 /* CompressData::to_bytes (comp.rs:279-300) with the W*8-bit tree */
 int huff_wcd_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
 /* CompressData::<L>::try_from_bytes (comp.rs:128-184) */
@@ -97,6 +122,26 @@ int huff_last_missing_wletter(void* out16, uint32_t* width);
 /* ---------------- device-resident job (bench / HBM-resident data) -------- */
 /* d_in: n letters of `width` bytes in HBM, 16-byte aligned */
 int huff_wenc_create(huff_ctx* ctx, uint32_t width, const void* d_in, size_t n, huff_wenc** out);
+/* A decode-only job over a foreign stream in HBM (comp_bytes bytes at d_comp,
+ * any alignment, `padding` unused bits in the last byte; e.g. one the
+ * reference wrote): the restart index is built on the device, as by
+ * huff_wcd_build_index, and stays there. *n_out = the stream's letters; the
+ * job has the tree's width. huff_wenc_decode and huff_wenc_decode_ranges then
+ * serve the stream with t (another tree: HUFF_E_STATE); huff_wenc_bits and
+ * huff_wenc_pack answer HUFF_E_STATE, the job has no letters to encode.
+ * Before any device work: HUFF_E_INVALID_ARG for a null argument,
+ * HUFF_E_EMPTY_COMP for comp_bytes = 0, HUFF_E_PADDING for padding > 7,
+ * HUFF_E_CODE_TOO_LONG for a code longer than 56 bits.
+ * Cost, measured on an MI355X on 1 GiB of letters (Zipf over 4,096 letters;
+ * tools/windexbench.py, DESIGN.md §9, "Index build"; an otherwise idle GPU, the stream spans of synchronous
+ * calls, medians of 10, two processes per width): the build takes 1.54-1.55 ms
+ * for 2-byte and 0.91 ms for 4-byte letters, against 1.57-1.58 and 1.00 ms
+ * for one huff_dev_wdecompress of the same stream: 0.98 and 0.91 of one
+ * index-free decode. The built job then decodes whole (huff_wenc_decode) in
+ * 0.57-0.58 / 0.47-0.48 ms and serves 1,000 ranges of 256 letters in 0.075 /
+ * 0.072 ms. */
+int huff_wenc_from_stream(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                          uint8_t padding, huff_wenc** out, uint64_t* n_out);
 void huff_wenc_free(huff_wenc* e);
 /* pass A: code lengths, restart index; *total_bits */
 int huff_wenc_bits(huff_wenc* e, const huff_wtree* t, uint64_t* total_bits);
@@ -140,7 +185,7 @@ int huff_wenc_decode_ranges(huff_wenc* e, const huff_wtree* t, const uint8_t* d_
  * only the blocks of the range are decoded (huff_wenc_decode_ranges); without
  * one (huff_wcd_new, huff_wcd_try_from_bytes) the stream is decoded whole by
  * the self-synchronising decoder and sliced: the slow route, which costs a
- * huff_wdecompress. HUFF_E_INVALID_ARG: the range is not inside the stream's
+ * huff_wdecompress and lasts until one huff_wcd_build_index. HUFF_E_INVALID_ARG: the range is not inside the stream's
  * letters; HUFF_E_BUFFER_TOO_SMALL: cap_letters < count; HUFF_E_CORRUPT: the
  * stream does not decode along its index. */
 int huff_wdecompress_range(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count,
