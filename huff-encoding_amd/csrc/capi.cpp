@@ -17,6 +17,7 @@
 
 #include "capi_util.hpp"
 #include "host/batch_container.hpp"
+#include "host/index_blob.hpp"
 
 namespace huff::capi {
 
@@ -64,6 +65,7 @@ uint64_t huff_diag_decode_index_form_launches(uint32_t i) { return huff::dev::de
 uint32_t huff_diag_range_index_forms(void) { return huff::dev::decode_ranges_index_forms(); }
 const char* huff_diag_range_index_form_name(uint32_t i) { return huff::dev::decode_ranges_index_form_name(i); }
 uint64_t huff_diag_range_index_form_launches(uint32_t i) { return huff::dev::decode_ranges_index_form_launches(i); }
+uint64_t huff_diag_range_staged_bytes(void) { return huff::range_staged_bytes(); }
 
 // --------------------------------------------------------------------------
 int huff_ctx_create(int device, huff_ctx** out) {
@@ -375,6 +377,27 @@ int huff_cd_index_view(const huff_compress_data* cd, uint64_t* n, const uint64_t
     return HUFF_OK;
 }
 
+int huff_cd_index_to_bytes(const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
+    if (!cd || !out_len || (!out && cap)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (!cd->index) return fail(HUFF_E_STATE, "the data carries no restart index (huff_cd_build_index)");
+    return guarded([&] {
+        const huff_index_host& idx = *cd->index;
+        uint64_t need = 0;
+        if (!huff::index_blob_size(idx.n, &need) || idx.chunk_start.size() != huff::index_chunk_entries(idx.n) ||
+            idx.sub_bit.size() != huff::index_marks(idx.n))
+            return huff::Status::err(HUFF_E_STATE, "the restart index does not have its letter count's shape");
+        *out_len = static_cast<size_t>(need);
+        if (cap < need) return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+        huff::index_blob_write(idx.n, cd->comp.size(), cd->padding, idx.chunk_start.data(), idx.sub_bit.data(), out);
+        return huff::Status::ok();
+    });
+}
+
+int huff_cd_attach_index(huff_ctx* ctx, huff_compress_data* cd, const uint8_t* blob, size_t len, uint64_t* n_out) {
+    if (!ctx || !cd || !blob || !n_out) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::attach_index_host(ctx, cd, blob, len, n_out); });
+}
+
 int huff_cd_to_bytes(const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
     if (!cd || !out_len) return fail(HUFF_E_INVALID_ARG, "null argument");
     return guarded([&] {
@@ -441,6 +464,22 @@ int huff_enc_from_stream(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_com
     return guarded([&] {
         auto e = std::make_unique<huff_enc>();
         HUFF_TRY(huff::build_index_dev(ctx, t, d_comp, comp_bytes, static_cast<uint64_t>(comp_bytes) * 8 - padding, *e));
+        *n_out = e->n;
+        *out = e.release();
+        return huff::Status::ok();
+    });
+}
+
+int huff_enc_from_indexed_stream(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, size_t comp_bytes,
+                                 uint8_t padding, const uint8_t* blob, size_t len, huff_enc** out, uint64_t* n_out) {
+    if (!ctx || !t || !out || !n_out || !blob || (!d_comp && comp_bytes)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    *out = nullptr;
+    *n_out = 0;
+    if (comp_bytes == 0) return fail(HUFF_E_EMPTY_COMP, "provided comp_bytes are empty");
+    if (padding > 7) return fail(HUFF_E_PADDING, "padding bits cannot be larger than 7");
+    return guarded([&] {
+        auto e = std::make_unique<huff_enc>();
+        HUFF_TRY(huff::attach_index_dev(ctx, t, d_comp, comp_bytes, padding, blob, len, *e, nullptr));
         *n_out = e->n;
         *out = e.release();
         return huff::Status::ok();

@@ -741,6 +741,29 @@ struct IndexPackArgs {
 };
 hipError_t launch_index_long(const IndexLongArgs& a, hipStream_t s);
 hipError_t launch_index_pack(const IndexPackArgs& a, hipStream_t s);
+// k_index_verify (index_verify.hip; host/index_verify_plan.hpp): whether
+// chunk_start[ceil(n / kChunk) + 1] and sub_bit[ceil(n / kIdx)], from outside,
+// are the index of this stream of n >= 1 letters under the tree of `lut`.
+// rec (u32[4], zeroed): [0] the kIndexBad* bits of what fails, [1] the
+// offending blocks' count, [2, 3] the first one recorded (u64, low word first).
+// Whatever the entries hold the kernel reads only them, comp's bytes up to the
+// dword holding the last of comp_bytes, and the table; it writes only rec.
+struct IndexVerifyArgs {
+    const uint8_t* comp;          // 4-B aligned
+    uint64_t comp_bytes;
+    uint64_t valid_bits;          // <= 8 comp_bytes
+    const uint32_t* lut;          // DecodeArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint16_t* stab;         // DecodeArgs::stab: the single-symbol table [1 << stab_bits], 4-B aligned
+    uint32_t stab_bits;           // 1 .. kSsMaxBits
+    uint32_t cu_count;
+    const uint64_t* chunk_start;
+    const uint32_t* sub_bit;
+    uint64_t n;
+    unsigned int* rec;
+};
+hipError_t launch_index_verify(const IndexVerifyArgs& a, hipStream_t s);
+size_t index_verify_lds_bytes(uint32_t stab_bits);
 // k_windex_pack (windex_build.hip; host/windex_plan.hpp): the same marks of
 // n >= 1 wide letters in the wide encoder's geometry, chunk_start[ceil(n /
 // kWideChunk) + 1] and sub_bit[ceil(n / kWideRun)]; *flag (zeroed) gets the

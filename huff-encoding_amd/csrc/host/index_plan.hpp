@@ -34,6 +34,10 @@ enum : uint32_t {
     kIndexBadOrder = 2,    // a mark at or before its predecessor
     kIndexBadEnd = 4,      // the end bit not in (last mark, valid_bits]
     kIndexBadOffset = 8,   // a mark 2^32 bits or more past its chunk's first
+    // k_index_verify's (index_verify_plan.hpp), of an index that came from outside:
+    kIndexBadForm = 16,    // sub_bit of a chunk's first mark is not 0 (the marks may be right: the split is not)
+    kIndexBadWalk = 32,    // a block's codes do not end exactly at the next mark (or the end bit)
+    kIndexBadTail = 64,    // another complete code fits between the end bit and valid_bits
 };
 
 // mark j of nmarks (>= 1): `mark` itself, `prev` = mark j - 1 (any value for

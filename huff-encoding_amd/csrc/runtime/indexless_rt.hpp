@@ -29,6 +29,19 @@ Status build_index_dev(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp,
 // huff_cd_build_index: the stream staged, build_index_dev, the index downloaded into cd
 Status build_index_host(huff_ctx* ctx, huff_compress_data* cd, uint64_t* n_out);
 
+// A stored index taken back (index_attach.cpp): the sidecar blob
+// (host/index_blob.hpp) parsed, tied to the stream by its comp_bytes and
+// padding, uploaded into the fresh job e and proved by k_index_verify; only
+// then is e a decode-only job of the blob's letters, as build_index_dev leaves
+// one. An all-8-bit tree and n = 0 are checked on the host, without a launch.
+// keep (may be null) receives the parsed arrays. HUFF_E_FROM_BYTES,
+// HUFF_E_INVALID_ARG (another stream's blob), HUFF_E_CODE_TOO_LONG,
+// HUFF_E_CORRUPT (any kIndexBad* flag).
+Status attach_index_dev(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, uint64_t comp_bytes, uint8_t padding,
+                        const uint8_t* blob, size_t len, huff_enc& e, huff_index_host* keep);
+// huff_cd_attach_index: the stream staged, attach_index_dev, the arrays kept in cd
+Status attach_index_host(huff_ctx* ctx, huff_compress_data* cd, const uint8_t* blob, size_t len, uint64_t* n_out);
+
 // The restart marks a decoder of the settled stream takes, one per 64 letters.
 enum class MarkForm {
     Compact,  // mark32 (u32 per mark) + task_seg (u32 per task): k_decode_fixed's skip build (dev::mark32_*)

@@ -2,6 +2,7 @@
 #include "runtime.hpp"
 
 #include "../host/range_plan.hpp"
+#include "../host/range_stage_plan.hpp"
 #include "indexless_rt.hpp"
 
 #include <algorithm>
@@ -1045,6 +1046,9 @@ Status decompress_host(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out
     return ctx->sync();
 }
 
+static std::atomic<uint64_t> g_range_staged{0};
+uint64_t range_staged_bytes() { return g_range_staged.load(std::memory_order_relaxed); }
+
 Status decompress_range_host(huff_ctx* ctx, const huff_compress_data* cd, uint64_t first, uint64_t count,
                              uint8_t* out, size_t cap) {
     const DecTables* dt = nullptr;
@@ -1069,18 +1073,32 @@ Status decompress_range_host(huff_ctx* ctx, const huff_compress_data* cd, uint64
     if (!range_inside(first, count, n)) return Status::err(HUFF_E_INVALID_ARG, "letter range outside the stream");
     if (cap < count) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
     if (count == 0) return Status::ok();
+    // only the touched blocks travel: a mini-stream of their bytes with a rebased index
+    const huff_index_host& full = *cd->index;
+    const RangeStage rs = range_stage(first, count, n, full.chunk_start.data(), full.sub_bit.data(), cd->comp.size());
+    huff_index_host mini;
+    if (rs.ok) {
+        mini.n = rs.n_mini;
+        mini.chunk_start.resize(index_chunk_entries(rs.n_mini));
+        mini.sub_bit.resize(index_marks(rs.n_mini));
+    }
+    if (!rs.ok || !range_stage_index(rs, full.chunk_start.data(), full.sub_bit.data(), mini.chunk_start.data(),
+                                     mini.sub_bit.data()))
+        return Status::err(HUFF_E_CORRUPT, "the stream does not decode along its restart index");
     HUFF_TRY(ctx->activate());
-    HUFF_TRY(ctx->d_in.ensure(cd->comp.size() + 16));
-    HIP_TRY(hipMemcpyAsync(ctx->d_in.p, cd->comp.data(), cd->comp.size(), hipMemcpyHostToDevice, ctx->stream));
+    HUFF_TRY(ctx->d_in.ensure(rs.nbytes + 16));
+    if (rs.nbytes)
+        HIP_TRY(hipMemcpyAsync(ctx->d_in.p, cd->comp.data() + rs.byte0, rs.nbytes, hipMemcpyHostToDevice, ctx->stream));
+    g_range_staged.fetch_add(rs.nbytes, std::memory_order_relaxed);
     HUFF_TRY(ctx->d_out.ensure(count + 16));
     huff_enc e;
     // the job's input pointer is unused by decode; give it the output staging (aligned)
-    HUFF_TRY(e.init(ctx, static_cast<const uint8_t*>(ctx->d_out.p), n));
-    HUFF_TRY(e.upload_index(*cd->index));
-    const uint64_t zero = 0;
+    HUFF_TRY(e.init(ctx, static_cast<const uint8_t*>(ctx->d_out.p), rs.n_mini));
+    HUFF_TRY(e.upload_index(mini));
+    const uint64_t zero = 0, first_mini = rs.first_mini;
     uint32_t st = 0;
-    HUFF_TRY(e.decode_ranges(cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), cd->comp.size(), &first, &count,
-                             &zero, 1, static_cast<uint8_t*>(ctx->d_out.p), count, &st));
+    HUFF_TRY(e.decode_ranges(cd->tree, static_cast<const uint8_t*>(ctx->d_in.p), rs.nbytes, &first_mini, &count, &zero, 1,
+                             static_cast<uint8_t*>(ctx->d_out.p), count, &st));
     if (st != HUFF_OK) return Status::err(static_cast<int>(st), "the stream does not decode along its restart index");
     HIP_TRY(hipMemcpyAsync(out, ctx->d_out.p, count, hipMemcpyDeviceToHost, ctx->stream));
     return ctx->sync();

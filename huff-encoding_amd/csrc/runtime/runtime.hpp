@@ -272,9 +272,13 @@ Status weights_threaded_from_host(huff_ctx* ctx, const uint8_t* bytes, size_t n,
 Status compress_host(huff_ctx* ctx, const uint8_t* bytes, size_t n, const huff_tree* t, huff_compress_data** out);
 Status decompress_host(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
 // the letters [first, first + count) of cd: through the range kernel when cd
-// has an index and a tree of at most kLongMaxLen bits, else decoded whole and sliced
+// has an index and a tree of at most kLongMaxLen bits (only the touched blocks'
+// bytes are staged, as a mini-stream: host/range_stage_plan.hpp), else decoded
+// whole and sliced
 Status decompress_range_host(huff_ctx* ctx, const huff_compress_data* cd, uint64_t first, uint64_t count,
                              uint8_t* out, size_t cap);
+// compressed bytes that decompress_range_host's indexed route has staged in this process
+uint64_t range_staged_bytes();
 Status file_compress(huff_ctx* ctx, const char* src, const char* dst, size_t block_size);
 Status file_decompress(huff_ctx* ctx, const char* src, const char* dst, size_t block_size);
 Status parse_block_size(const char* s, size_t* out);

@@ -458,6 +458,36 @@ class CompressData:
         sub_bit = np.ctypeslib.as_array(sb, (ns.value,)).copy() if ns.value else np.zeros(0, np.uint32)
         return n.value, chunk_start, sub_bit
 
+    def index_to_bytes(self) -> bytes:
+        """the attached restart index as a sidecar blob to store beside
+        to_bytes(), which holds none (huff_cd_index_to_bytes; the layout is in
+        include/huffgpu.h). HuffError(STATE) without an index."""
+        n = C.c_size_t()
+        rc = load().huff_cd_index_to_bytes(self.h, None, 0, C.byref(n))
+        if rc not in (_lib.HUFF_OK, _lib.E_BUFFER_TOO_SMALL):
+            _check(rc)
+        buf = (C.c_uint8 * max(n.value, 1))()
+        _check(load().huff_cd_index_to_bytes(self.h, buf, n.value, C.byref(n)))
+        return C.string_at(buf, n.value)
+
+    def attach_index(self, blob, ctx: Optional["Context"] = None) -> int:
+        """a stored index_to_bytes() blob taken back (huff_cd_attach_index): parsed,
+        uploaded and proved on the GPU to be this stream's index under this
+        tree, and only then attached; decompress and decompress_range then take
+        their indexed routes. Returns the stream's letter count. HuffError
+        FROM_BYTES (the blob does not parse), INVALID_ARG (another stream's
+        blob), STATE (an index is already attached), CODE_TOO_LONG (codes past
+        57 bits) or CORRUPT (the entries are not this stream's index); the
+        data is unchanged after any of them."""
+        ctx = ctx or default_context()
+        keep, addr, nb = _buf(blob)
+        if not nb:  # an empty blob is a blob that does not parse, not a null pointer
+            keep = C.create_string_buffer(1)
+            addr = C.addressof(keep)
+        n = C.c_uint64()
+        _check(load().huff_cd_attach_index(ctx.h, self.h, addr, nb, C.byref(n)))
+        return n.value
+
     def to_bytes(self) -> bytes:
         """comp.rs:279-300"""
         n = C.c_size_t()

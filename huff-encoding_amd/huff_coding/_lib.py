@@ -93,9 +93,12 @@ SIGNATURES = [
     ("huff_compress_with_tree", i, [vp, vp, sz, vp, C.POINTER(vp)]),
     ("huff_compress_bytes", i, [vp, vp, sz, C.POINTER(vp)]),
     ("huff_decompress", i, [vp, vp, u8p, sz, szp]),
+    ("huff_cd_index_to_bytes", i, [vp, u8p, sz, szp]),
+    ("huff_cd_attach_index", i, [vp, vp, vp, sz, u64p]),
     ("huff_decompress_range", i, [vp, vp, C.c_uint64, C.c_uint64, u8p, sz]),
     ("huff_enc_create", i, [vp, vp, sz, C.POINTER(vp)]),
     ("huff_enc_from_stream", i, [vp, vp, vp, sz, C.c_uint8, C.POINTER(vp), u64p]),
+    ("huff_enc_from_indexed_stream", i, [vp, vp, vp, sz, C.c_uint8, vp, sz, C.POINTER(vp), u64p]),
     ("huff_enc_free", None, [vp]),
     ("huff_enc_hist", i, [vp, vp]),
     ("huff_enc_hist_row", i, [vp, vp]),
@@ -145,6 +148,7 @@ SIGNATURES = [
     ("huff_diag_range_index_forms", C.c_uint32, []),
     ("huff_diag_range_index_form_name", C.c_char_p, [C.c_uint32]),
     ("huff_diag_range_index_form_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_diag_range_staged_bytes", C.c_uint64, []),
     # include/huffgpu_wide.h
     ("huff_wtree_from_weights", i, [C.c_uint32, vp, vp, sz, C.POINTER(vp)]),
     ("huff_wtree_clone", i, [vp, C.POINTER(vp)]),
@@ -232,6 +236,11 @@ def range_index_form_launches() -> dict:
     L = load()
     return {L.huff_diag_range_index_form_name(k).decode(): L.huff_diag_range_index_form_launches(k)
             for k in range(L.huff_diag_range_index_forms())}
+
+
+def range_staged_bytes() -> int:
+    """compressed bytes that decompress_range's indexed route has staged so far (huff_diag_range_staged_bytes)"""
+    return int(load().huff_diag_range_staged_bytes())
 
 
 def wide_build_launches() -> dict:

@@ -31,17 +31,28 @@ class EncodeJob:
         _check(load().huff_enc_create(ctx.h, C.c_void_p(d_in), n, C.byref(self.h)))
 
     @classmethod
-    def from_stream(cls, ctx, tree, comp_ptr: int, comp_bytes: int, padding: int) -> "EncodeJob":
+    def from_stream(cls, ctx, tree, comp_ptr: int, comp_bytes: int, padding: int, index=None) -> "EncodeJob":
         """a decode-only job over a foreign stream in HBM (huff_enc_from_stream):
         comp_bytes bytes at comp_ptr (any alignment), the last with `padding`
         pad bits. Its restart index is built on the device and stays there;
         .n is the stream's letter count. decode() and decode_ranges() serve it
-        with the same tree; the encode calls raise HuffError(STATE)."""
+        with the same tree; the encode calls raise HuffError(STATE).
+        index: a stored CompressData.index_to_bytes() blob of this stream
+        (huff_enc_from_indexed_stream): uploaded and proved on the device
+        instead of built; HuffError(CORRUPT) if it is not this stream's index."""
         job = cls.__new__(cls)
         job.ctx = ctx
         job.n = 0
         job.h = C.c_void_p()
         n = C.c_uint64()
+        if index is not None:
+            blob = np.frombuffer(index, np.uint8)  # no copy: a blob is 4 bytes per 64 letters
+            keep = blob if blob.size else np.zeros(1, np.uint8)
+            _check(load().huff_enc_from_indexed_stream(
+                ctx.h, tree.h, C.c_void_p(comp_ptr) if comp_ptr else None, comp_bytes, padding,
+                C.c_void_p(keep.ctypes.data), blob.size, C.byref(job.h), C.byref(n)))
+            job.n = n.value
+            return job
         _check(load().huff_enc_from_stream(ctx.h, tree.h, C.c_void_p(comp_ptr) if comp_ptr else None, comp_bytes,
                                            padding, C.byref(job.h), C.byref(n)))
         job.n = n.value

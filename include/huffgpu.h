@@ -187,9 +187,53 @@ int huff_cd_build_index(huff_ctx* ctx, huff_compress_data* cd, uint64_t* n_out);
  * chunk_start[*nchunk_entries] (the
  * first bit of every 65,536-letter chunk, then the stream's end bit) and
  * sub_bit[*nsub] (the first bit of every 64th letter, from its chunk's).
- * HUFF_E_STATE without an index. This is also how a caller persists one. */
+ * HUFF_E_STATE without an index. huff_cd_index_to_bytes writes the same arrays
+ * as a blob that huff_cd_attach_index takes back. */
 int huff_cd_index_view(const huff_compress_data* cd, uint64_t* n, const uint64_t** chunk_start,
                        size_t* nchunk_entries, const uint32_t** sub_bit, size_t* nsub);
+/* cd's restart index as a sidecar blob to store beside huff_cd_to_bytes (which
+ * is the reference's format and holds no index). Little-endian:
+ *   "HFX1"  u32 reserved (0)  u64 n  u64 comp_bytes  u8 padding  7 x 0
+ *   u64 nchunk_entries  u64 nsub
+ *   u64 chunk_start[nchunk_entries]   u32 sub_bit[nsub]
+ * with nchunk_entries = ceil(n / 65,536) + 1 and nsub = ceil(n / 64), the arrays
+ * of huff_cd_index_view; comp_bytes and padding are cd's, and tie the blob to
+ * its stream. *out_len = the blob's bytes (48 + 8 nchunk_entries + 4 nsub).
+ * HUFF_E_STATE without an index; HUFF_E_BUFFER_TOO_SMALL when cap is short,
+ * with *out_len = the size needed (out may be NULL with cap 0). No device work. */
+int huff_cd_index_to_bytes(const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
+/* A stored index taken back: the blob is parsed, the stream staged to the
+ * device, the entries uploaded and proved there, and only then attached. The
+ * proof (k_index_verify) accepts the entries if and only if they are the ones
+ * huff_cd_build_index would build for this stream and tree: mark 0 is bit 0,
+ * the marks strictly increase and the end bit lies in (last mark, valid bits],
+ * sub_bit is 0 at every 65,536-letter chunk's first mark; from every mark
+ * exactly min(64, n - 64 j) codes end exactly at the next one (the last block:
+ * at the end bit); and at the end bit no further complete code fits. Only code
+ * lengths are read and no letter is written: no n-byte buffer exists in the
+ * call. Whatever the blob holds, the kernel reads only the index entries, the
+ * stream's bytes and the tree's table, and writes only its flag record. An
+ * all-8-bit tree (unless HUFF_DISABLE_FIXED8=1) and n = 0 (acceptable only as
+ * chunk_start = {0} for a stream without one complete code) are checked on the
+ * host, without a launch.
+ * Afterwards huff_cd_has_index is 1, and huff_decompress and
+ * huff_decompress_range take their indexed routes; *n_out = n.
+ * HUFF_E_FROM_BYTES: the blob does not parse (short, bad magic, non-zero
+ * reserved bytes, counts that disagree with n, an n too large, trailing bytes);
+ * HUFF_E_INVALID_ARG: a null pointer, or the blob's comp_bytes or padding are
+ * not cd's; HUFF_E_STATE: cd already has an index; HUFF_E_CODE_TOO_LONG: a tree
+ * with a code longer than 57 bits; HUFF_E_CORRUPT: any check failed (the error
+ * text names them and the first offending block). On every error cd is
+ * unchanged. Not thread-safe against concurrent readers of the same cd.
+ * Cost (MI355X, 1 GiB streams; DESIGN.md §12, "Storing and re-attaching the
+ * index"): the proof kernel takes 1.05-1.10 ms, about what building the index
+ * takes (1.09-1.10 ms in the same session), not the 0.4 ms that was hoped for;
+ * the entries are 4 bytes per 64 letters from host memory, 64 MiB and 1.3 ms
+ * more. Attaching is therefore NOT cheaper than huff_cd_build_index on the
+ * device side; what it saves is a second source of truth: a stored index is
+ * re-used only after the same proof the build would give. In both calls on a
+ * CompressData the staging of the stream itself (host to device) dominates. */
+int huff_cd_attach_index(huff_ctx* ctx, huff_compress_data* cd, const uint8_t* blob, size_t len, uint64_t* n_out);
 /* CompressData::to_bytes (comp.rs:279-300) */
 int huff_cd_to_bytes(const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
 /* CompressData::try_from_bytes (comp.rs:128-184) */
@@ -211,8 +255,10 @@ int huff_decompress(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out, s
 /* The letters [first, first + count) of huff_decompress's output, in out[0,
  * count) (host memory, cap bytes). A CompressData that carries a restart index
  * (one from huff_compress_*) and a tree of at most 57 bits decodes only the
- * touched 64-letter blocks (huff_enc_decode_ranges' kernel; the whole stream
- * is still staged to the device). One without an index (huff_cd_new,
+ * touched 64-letter blocks (huff_enc_decode_ranges' kernel) and stages only
+ * their bytes: the span from the first touched block's restart point, rounded
+ * down to 16 bytes, to the last one's end plus 16 bytes of look-ahead, as a
+ * small stream with a rebased index (huff_diag_range_staged_bytes counts them). One without an index (huff_cd_new,
  * huff_cd_try_from_bytes) or with a deeper tree takes the slow route: it is
  * decoded whole and sliced. A stream without an index leaves the slow route
  * for good after one huff_cd_build_index. HUFF_E_INVALID_ARG: the range is not inside the
@@ -337,6 +383,21 @@ int huff_enc_decode_ranges(huff_enc* e, const huff_tree* t, const uint8_t* d_com
  * huff_enc_free. */
 int huff_enc_from_stream(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, size_t comp_bytes,
                          uint8_t padding, huff_enc** out, uint64_t* n_out);
+/* huff_enc_from_stream with the restart-point step replaced by the upload and
+ * proof of a stored index (a huff_cd_index_to_bytes blob in host memory; the
+ * checks and statuses are huff_cd_attach_index's, plus HUFF_E_EMPTY_COMP /
+ * HUFF_E_PADDING): a decode-only job of the blob's n letters that remembers
+ * t's codes. d_comp may have any alignment for this call (a stream not 16-B
+ * aligned is first copied to an aligned buffer of the context); the encode
+ * calls on the job return HUFF_E_STATE; *out is NULL on any error.
+ * Cost (MI355X, 1 GiB streams, same session; DESIGN.md §12, "Storing and
+ * re-attaching the index"): 2.38-2.42 ms against huff_enc_from_stream's
+ * 1.09-1.10 ms, a ratio of 2.15-2.21: this call is SLOWER than building. The
+ * proof kernel alone is 1.05-1.10 ms (0.95-1.01 of the build), the upload of
+ * the 64 MiB of entries the rest. Use it where the entries must be the stored
+ * ones; where only an index is wanted, huff_enc_from_stream is the faster call. */
+int huff_enc_from_indexed_stream(huff_ctx* ctx, const huff_tree* t, const uint8_t* d_comp, size_t comp_bytes,
+                                 uint8_t padding, const uint8_t* blob, size_t len, huff_enc** out, uint64_t* n_out);
 
 /* ------------------------------------------------------------------------ */
 /* multi-GPU: sharded compress over an RCCL communicator  */
@@ -677,6 +738,10 @@ uint64_t huff_diag_decode_index_form_launches(uint32_t i);
 uint32_t huff_diag_range_index_forms(void);
 const char* huff_diag_range_index_form_name(uint32_t i);
 uint64_t huff_diag_range_index_form_launches(uint32_t i);
+/* The compressed bytes that huff_decompress_range's indexed route has staged to
+ * a device in this process (one relaxed counter): a small range of a large
+ * stream adds about its touched blocks' bytes, not the stream's. */
+uint64_t huff_diag_range_staged_bytes(void);
 
 #ifdef __cplusplus
 }
