@@ -207,6 +207,16 @@ int huff_wcd_index_view(const huff_wcompress_data* cd, uint64_t* n, const uint64
     return HUFF_OK;
 }
 
+int huff_wcd_index_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
+    if (!cd || !out_len || (!out && cap)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::windex_to_bytes(cd, out, cap, out_len); });
+}
+
+int huff_wcd_attach_index(huff_ctx* ctx, huff_wcompress_data* cd, const uint8_t* blob, size_t len, uint64_t* n_out) {
+    if (!ctx || !cd || !blob || !n_out) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::wattach_index_host(ctx, cd, blob, len, n_out); });
+}
+
 int huff_wcd_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
     if (!cd || !out_len) return fail(HUFF_E_INVALID_ARG, "null argument");
     return guarded([&] {
@@ -299,6 +309,22 @@ int huff_wenc_from_stream(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_c
     });
 }
 
+int huff_wenc_from_indexed_stream(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                                  uint8_t padding, const uint8_t* blob, size_t len, huff_wenc** out, uint64_t* n_out) {
+    if (!ctx || !t || !out || !n_out || !blob || (!d_comp && comp_bytes)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    *out = nullptr;
+    *n_out = 0;
+    if (comp_bytes == 0) return fail(HUFF_E_EMPTY_COMP, "provided comp_bytes are empty");
+    if (padding > 7) return fail(HUFF_E_PADDING, "padding bits cannot be larger than 7");
+    return guarded([&] {
+        auto e = std::make_unique<huff_wenc>();
+        HUFF_TRY(huff::wattach_index_dev(ctx, t, d_comp, comp_bytes, padding, blob, len, *e, nullptr));
+        *n_out = e->n;
+        *out = e.release();
+        return huff::Status::ok();
+    });
+}
+
 void huff_wenc_free(huff_wenc* e) {
     if (!e) return;
     if (e->ctx) hipSetDevice(e->ctx->device);
@@ -350,7 +376,7 @@ int huff_wdecompress_range(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_
                            size_t cap_letters) {
     if (!ctx || !cd || (!out && cap_letters)) return fail(HUFF_E_INVALID_ARG, "null argument");
     return guarded([&] {
-        return huff::wdecompress_range_host(ctx, cd, first, count, static_cast<uint8_t*>(out), cap_letters);
+        return huff::wdecompress_range_staged_host(ctx, cd, first, count, static_cast<uint8_t*>(out), cap_letters);
     });
 }
 
@@ -378,6 +404,7 @@ uint64_t huff_diag_wide_index_form_launches(uint32_t i) { return huff::dev::wide
 uint32_t huff_diag_wrange_builds(void) { return huff::dev::wide_range_builds(); }
 const char* huff_diag_wrange_build_name(uint32_t i) { return huff::dev::wide_range_build_name(i); }
 uint64_t huff_diag_wrange_build_launches(uint32_t i) { return huff::dev::wide_range_build_launches(i); }
+uint64_t huff_diag_wrange_staged_bytes(void) { return huff::wrange_staged_bytes(); }
 
 int huff_wtree_diag(const huff_wtree* t, uint64_t out[HUFF_WTREE_DIAG_WORDS]) {
     if (!t || !out) return fail(HUFF_E_INVALID_ARG, "null argument");

@@ -778,6 +778,31 @@ struct WIndexPackArgs {
     unsigned int* flag;
 };
 hipError_t launch_windex_pack(const WIndexPackArgs& a, hipStream_t s);
+// k_windex_verify (windex_verify.hip; host/windex_verify_plan.hpp):
+// k_index_verify for the wide geometry, chunk_start[ceil(n / kWideChunk) + 1]
+// and sub_bit[ceil(n / kWideRun)] from outside, n >= 1; `lut` and `stab` are
+// the tables of the wide tree's shape (code lengths only: one kernel for every
+// letter width). rec as IndexVerifyArgs::rec. stage_bytes: the LDS stage per
+// wave, wverify_stage_bytes(valid_bits, n). The same contract: the kernel
+// reads only the entries, comp's bytes up to the dword holding the last of
+// comp_bytes, and the tables; it writes only rec.
+struct WIndexVerifyArgs {
+    const uint8_t* comp;          // 4-B aligned
+    uint64_t comp_bytes;
+    uint64_t valid_bits;          // <= 8 comp_bytes
+    const uint32_t* lut;
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint16_t* stab;         // [1 << stab_bits], 4-B aligned
+    uint32_t stab_bits;           // 1 .. kSsMaxBits
+    uint32_t cu_count;
+    uint32_t stage_bytes;         // a multiple of 128 in [kWVerifyStageMin, kWVerifyStageMax]
+    const uint64_t* chunk_start;
+    const uint32_t* sub_bit;
+    uint64_t n;
+    unsigned int* rec;
+};
+hipError_t launch_windex_verify(const WIndexVerifyArgs& a, hipStream_t s);
+size_t windex_verify_lds_bytes(uint32_t stab_bits, uint32_t stage_bytes);
 hipError_t launch_bytemap(const BytemapArgs& a, hipStream_t s);
 // letter checksums of the decode check build (checksum.hip): per task of
 // kTaskSym letters, sum and position-weighted sum (u64 = s2 << 32 | s1);

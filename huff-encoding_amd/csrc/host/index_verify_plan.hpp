@@ -94,7 +94,8 @@ HUFF_HD constexpr VerifyLane verify_lane(uint64_t j, uint64_t n, uint64_t base, 
 
 // The task's staged span: first = its first mark, tend = the bit after it.
 // staged: bytes [b0, b0 + len) (b0 a multiple of 16, len of 16 and <=
-// kVerifyStage) hold every word a walk inside [first, tend] reads. Not staged
+// stage, k_index_verify's kVerifyStage unless given: k_windex_verify sizes its
+// own per launch) hold every word a walk inside [first, tend] reads. Not staged
 // (the marks are out of order or past the stream, or the span is too long):
 // the lanes that may walk do so through the checked source.
 struct VerifySpan {
@@ -102,11 +103,12 @@ struct VerifySpan {
     uint64_t b0;
     uint32_t len;
 };
-HUFF_HD constexpr VerifySpan verify_span(uint64_t first, uint64_t tend, uint64_t valid_bits) {
+HUFF_HD constexpr VerifySpan verify_span(uint64_t first, uint64_t tend, uint64_t valid_bits,
+                                         uint32_t stage = kVerifyStage) {
     if (!(first < tend && tend <= valid_bits)) return {false, 0, 0};
     const uint64_t b0 = (first >> 3) & ~15ull;
     const uint64_t b1 = (((tend + 7) >> 3) + kVerifyMargin + 15) & ~15ull;  // tend <= valid_bits < 2^63: no wrap
-    if (b1 - b0 > kVerifyStage) return {false, 0, 0};
+    if (b1 - b0 > stage) return {false, 0, 0};
     return {true, b0, static_cast<uint32_t>(b1 - b0)};
 }
 // the staged bytes that are loaded: the rest of [b0, b0 + len) reads as zero.

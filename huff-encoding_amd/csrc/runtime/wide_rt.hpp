@@ -95,4 +95,27 @@ Status wbuild_index_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_com
                         uint64_t valid_bits, huff_wenc& e);
 // huff_wcd_build_index: the stream staged, wbuild_index_dev, the index downloaded into cd
 Status wbuild_index_host(huff_ctx* ctx, huff_wcompress_data* cd, uint64_t* n_out);
+
+// A stored wide index taken back (windex_attach.cpp): the sidecar blob
+// (host/windex_blob.hpp) parsed, tied to the stream by its width, comp_bytes and
+// padding, uploaded into the fresh job e and proved by k_windex_verify on the
+// tree's shape; only then is e a decode-only job of the blob's letters, as
+// wbuild_index_dev leaves one. n = 0 is checked on the host, without a launch.
+// keep (may be null) receives the parsed arrays. HUFF_E_FROM_BYTES,
+// HUFF_E_INVALID_ARG (another stream's blob), HUFF_E_CODE_TOO_LONG,
+// HUFF_E_CORRUPT (any kIndexBad* flag).
+Status wattach_index_dev(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, uint64_t comp_bytes, uint8_t padding,
+                         const uint8_t* blob, size_t len, huff_wenc& e, huff_index_host* keep);
+// huff_wcd_attach_index: the stream staged, wattach_index_dev, the arrays kept in cd
+Status wattach_index_host(huff_ctx* ctx, huff_wcompress_data* cd, const uint8_t* blob, size_t len, uint64_t* n_out);
+// huff_wcd_index_to_bytes: cd's index as the blob; no device work
+Status windex_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
+// huff_wdecompress_range: with an index only the touched blocks' bytes are
+// staged, as a mini-stream (host/wrange_stage_plan.hpp); without one,
+// wdecompress_range_host's slow route
+Status wdecompress_range_staged_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count,
+                                     uint8_t* out, size_t cap_letters);
+// the compressed bytes wdecompress_range_staged_host has copied to the device
+// since the library was loaded (huff_diag_wrange_staged_bytes)
+uint64_t wrange_staged_bytes();
 }  // namespace huff

@@ -196,6 +196,10 @@ SIGNATURES = [
     ("huff_wcd_build_index", i, [vp, vp, u64p]),
     ("huff_wcd_index_view", i, [vp, u64p, C.POINTER(u64p), szp, C.POINTER(C.POINTER(C.c_uint32)), szp]),
     ("huff_wenc_from_stream", i, [vp, vp, vp, sz, C.c_uint8, C.POINTER(vp), u64p]),
+    ("huff_wcd_index_to_bytes", i, [vp, u8p, sz, szp]),
+    ("huff_wcd_attach_index", i, [vp, vp, vp, sz, u64p]),
+    ("huff_wenc_from_indexed_stream", i, [vp, vp, vp, sz, C.c_uint8, vp, sz, C.POINTER(vp), u64p]),
+    ("huff_diag_wrange_staged_bytes", C.c_uint64, []),
 ]
 
 _lib = None
@@ -241,6 +245,12 @@ def range_index_form_launches() -> dict:
 def range_staged_bytes() -> int:
     """compressed bytes that decompress_range's indexed route has staged so far (huff_diag_range_staged_bytes)"""
     return int(load().huff_diag_range_staged_bytes())
+
+
+def wrange_staged_bytes() -> int:
+    """compressed bytes that the wide decompress_range's indexed route has staged so far
+    (huff_diag_wrange_staged_bytes; range_staged_bytes counts the byte path's only)"""
+    return int(load().huff_diag_wrange_staged_bytes())
 
 
 def wide_build_launches() -> dict:

@@ -287,6 +287,34 @@ class WideCompressData:
         sub_bit = np.ctypeslib.as_array(sb, (ns.value,)).copy() if ns.value else np.zeros(0, np.uint32)
         return n.value, chunk_start, sub_bit
 
+    def index_to_bytes(self) -> bytes:
+        """the attached restart index as a sidecar blob ("HFW1") to store beside
+        to_bytes(), which holds none (huff_wcd_index_to_bytes; the layout is in
+        include/huffgpu_wide.h). HuffError(STATE) without an index."""
+        n = C.c_size_t()
+        rc = load().huff_wcd_index_to_bytes(self.h, None, 0, C.byref(n))
+        if rc not in (_lib.HUFF_OK, _lib.E_BUFFER_TOO_SMALL):
+            _check(rc)
+        buf = (C.c_uint8 * max(n.value, 1))()
+        _check(load().huff_wcd_index_to_bytes(self.h, buf, n.value, C.byref(n)))
+        return C.string_at(buf, n.value)
+
+    def attach_index(self, blob, ctx=None) -> int:
+        """a stored index_to_bytes() blob taken back (huff_wcd_attach_index):
+        parsed, uploaded and proved on the GPU to be this stream's index under
+        this tree, and only then attached; decompress and decompress_range then
+        take their indexed routes, also for trees with codes of 33-56 bits.
+        Returns the stream's letter count. HuffError FROM_BYTES (the blob does
+        not parse), INVALID_ARG (another stream's or another width's blob),
+        STATE (an index is already attached), CODE_TOO_LONG (codes past 56
+        bits) or CORRUPT (the entries are not this stream's index); the data
+        is unchanged after any of them."""
+        b = np.frombuffer(blob, np.uint8)
+        keep = b if b.size else np.zeros(1, np.uint8)  # an empty blob does not parse; it is not a null pointer
+        n = C.c_uint64()
+        _check(load().huff_wcd_attach_index(_ctx(ctx).h, self.h, C.c_void_p(keep.ctypes.data), b.size, C.byref(n)))
+        return n.value
+
     def to_bytes(self) -> bytes:
         n = C.c_size_t()
         rc = load().huff_wcd_to_bytes(self.h, None, 0, C.byref(n))
@@ -387,13 +415,17 @@ class WideEncodeJob:
         _check(load().huff_wenc_create(ctx.h, width, C.c_void_p(d_in), n, C.byref(self.h)))
 
     @classmethod
-    def from_stream(cls, ctx, tree: WideTree, comp_ptr: int, comp_bytes: int, padding: int) -> "WideEncodeJob":
+    def from_stream(cls, ctx, tree: WideTree, comp_ptr: int, comp_bytes: int, padding: int,
+                    index=None) -> "WideEncodeJob":
         """a decode-only job over a foreign stream in HBM (huff_wenc_from_stream):
         comp_bytes bytes at comp_ptr (any alignment), the last with `padding`
         pad bits. Its restart index is built on the device and stays there;
         .n is the stream's letter count, .width the tree's. decode() and
         decode_ranges() serve it with the same tree (kept alive as .tree);
-        bits() and pack() raise HuffError(STATE)."""
+        bits() and pack() raise HuffError(STATE).
+        index: a stored WideCompressData.index_to_bytes() blob of this stream
+        (huff_wenc_from_indexed_stream): uploaded and proved on the device
+        instead of built; HuffError(CORRUPT) if it is not this stream's index."""
         job = cls.__new__(cls)
         job.ctx = ctx
         job.tree = tree
@@ -401,6 +433,14 @@ class WideEncodeJob:
         job.width = tree.ltype.width
         job.h = C.c_void_p()
         n = C.c_uint64()
+        if index is not None:
+            blob = np.frombuffer(index, np.uint8)  # no copy: a blob is 4 bytes per 64 letters
+            keep = blob if blob.size else np.zeros(1, np.uint8)
+            _check(load().huff_wenc_from_indexed_stream(
+                ctx.h, tree.h, C.c_void_p(comp_ptr) if comp_ptr else None, comp_bytes, padding,
+                C.c_void_p(keep.ctypes.data), blob.size, C.byref(job.h), C.byref(n)))
+            job.n = n.value
+            return job
         _check(load().huff_wenc_from_stream(ctx.h, tree.h, C.c_void_p(comp_ptr) if comp_ptr else None, comp_bytes,
                                             padding, C.byref(job.h), C.byref(n)))
         job.n = n.value

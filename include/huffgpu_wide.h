@@ -99,6 +99,43 @@ int huff_wcd_build_index(huff_ctx* ctx, huff_wcompress_data* cd, uint64_t* n_out
  * huff_wcompress_with_tree shows the encoder's. */
 int huff_wcd_index_view(const huff_wcompress_data* cd, uint64_t* n, const uint64_t** chunk_start,
                         size_t* nchunk_entries, const uint32_t** sub_bit, size_t* nsub);
+/* cd's restart index as a sidecar blob, to be stored beside huff_wcd_to_bytes'
+ * container (which is the reference's and holds no index) and taken back by
+ * huff_wcd_attach_index or huff_wenc_from_indexed_stream. Little-endian, 48
+ * bytes of header as the byte streams' "HFX1":
+ *   "HFW1"  u32 width (1, 2, 4, 8 or 16)  u64 n  u64 comp_bytes  u8 padding  7 x 0
+ *   u64 nchunk_entries  u64 nsub
+ *   u64 chunk_start[nchunk_entries]   u32 sub_bit[nsub]
+ * with the arrays of huff_wcd_index_view: 48 + 8 (ceil(n / 16384) + 1) +
+ * 4 ceil(n / 64) bytes. *out_len = that size; HUFF_E_BUFFER_TOO_SMALL when cap
+ * is less (out may be NULL with cap 0, to ask for the size), HUFF_E_STATE
+ * without an index. No device work. */
+int huff_wcd_index_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
+/* Takes a stored index back into a cd that has none (huff_wcd_new,
+ * huff_wcd_try_from_bytes). The blob is not trusted: the stream and the
+ * entries are staged to the device and k_windex_verify proves that they are
+ * exactly what huff_wcd_build_index would write for this stream and tree: mark
+ * 0 is bit 0, the marks strictly increase, sub_bit is 0 at every 256th mark,
+ * from every mark exactly 64 codes (the last block: its letters) end exactly at
+ * the next, and after the end bit no further complete code fits. Only then is
+ * the index kept: huff_wcd_has_index is 1, huff_wdecompress and
+ * huff_wdecompress_range take their indexed routes, trees with codes of 33-56
+ * bits included. *n_out = the letters.
+ * Errors, in this order, cd unchanged on each: HUFF_E_INVALID_ARG for a null
+ * pointer; HUFF_E_FROM_BYTES when the blob does not parse (short, another
+ * magic such as "HFX1", a width not of the five, non-zero pad bytes, counts
+ * that disagree with n, n >= 2^60, trailing bytes); HUFF_E_INVALID_ARG when the
+ * blob's width, comp_bytes or padding are not cd's; HUFF_E_STATE when cd has an
+ * index; HUFF_E_CODE_TOO_LONG for a code longer than 56 bits; HUFF_E_CORRUPT
+ * when a check fails (huff_last_error names the checks and the first block).
+ * n = 0 is accepted only as chunk_start = {0} for a stream whose first bits
+ * hold no complete code, by a host check.
+ * Cost: that of huff_wenc_from_indexed_stream plus the stream's copy to the
+ * device. Measured there on Zipf streams over 4,096 letters, attaching is
+ * SLOWER than building (1.25-1.38 times huff_wenc_from_stream on 1 GiB of
+ * letters): where any index will do, huff_wcd_build_index is the faster call
+ * on such streams. */
+int huff_wcd_attach_index(huff_ctx* ctx, huff_wcompress_data* cd, const uint8_t* blob, size_t len, uint64_t* n_out);
 /* CompressData::to_bytes (comp.rs:279-300) with the W*8-bit tree */
 int huff_wcd_to_bytes(const huff_wcompress_data* cd, uint8_t* out, size_t cap, size_t* out_len);
 /* CompressData::<L>::try_from_bytes (comp.rs:128-184) */
@@ -142,6 +179,27 @@ int huff_wenc_create(huff_ctx* ctx, uint32_t width, const void* d_in, size_t n, 
  * 0.072 ms. */
 int huff_wenc_from_stream(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
                           uint8_t padding, huff_wenc** out, uint64_t* n_out);
+/* huff_wenc_from_stream with the build replaced by upload and proof: the index
+ * comes from a blob of huff_wcd_index_to_bytes, goes to the device straight
+ * from it and is proved there as by huff_wcd_attach_index. The result is the
+ * same decode-only job; d_comp at any alignment. Pre-checks as
+ * huff_wenc_from_stream's, then huff_wcd_attach_index's errors (no
+ * HUFF_E_STATE: the job is new); *out is NULL on any error.
+ * Cost, measured on an MI355X on 1 GiB of letters (Zipf over 4,096 letters;
+ * 7.82 bits per letter; tools/wattachbench.py, DESIGN.md §9, "Storing and
+ * re-attaching the index"; the stream spans of synchronous calls, medians of
+ * 10, two processes, building and attaching alternating): attaching takes 2.15
+ * ms for 2-byte and 1.15 ms for 4-byte letters, against 1.56-1.58 and 0.91-0.93
+ * ms for huff_wenc_from_stream in the same session: 1.36-1.38 and 1.25-1.26
+ * times the build. BUILDING IS THE FASTER CALL. The proof kernel alone takes
+ * 1.36 / 0.64 ms (0.86-0.87 / 0.69-0.71 of the build); the rest is mostly the
+ * entries' copy from host memory (4 bytes per 64 letters). Use this call to
+ * re-use stored entries, proved, not to get an index cheaply. The attached job
+ * decodes whole in 0.60 / 0.48 ms, as the built one. (One noisier process on a
+ * 60,000-letter alphabet, 9.45 bits per letter, went the other way: 6.7 / 4.3
+ * ms against 8.8 / 6.4 ms for building.) */
+int huff_wenc_from_indexed_stream(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                                  uint8_t padding, const uint8_t* blob, size_t len, huff_wenc** out, uint64_t* n_out);
 void huff_wenc_free(huff_wenc* e);
 /* pass A: code lengths, restart index; *total_bits */
 int huff_wenc_bits(huff_wenc* e, const huff_wtree* t, uint64_t* total_bits);
@@ -187,7 +245,16 @@ int huff_wenc_decode_ranges(huff_wenc* e, const huff_wtree* t, const uint8_t* d_
  * the self-synchronising decoder and sliced: the slow route, which costs a
  * huff_wdecompress and lasts until one huff_wcd_build_index. HUFF_E_INVALID_ARG: the range is not inside the stream's
  * letters; HUFF_E_BUFFER_TOO_SMALL: cap_letters < count; HUFF_E_CORRUPT: the
- * stream does not decode along its index. */
+ * stream does not decode along its index.
+ * With an index only the touched blocks' compressed bytes go to the device, as
+ * a small stream of their own with a rebased index: from the 16-byte boundary
+ * at or before the first touched block's first bit through the byte of the
+ * last touched bit and 16 more, never past the stream.
+ * huff_diag_wrange_staged_bytes counts them. Measured on an MI355X (DESIGN.md
+ * §9, "Storing and re-attaching the index"): a 256-letter range of 1 GiB of
+ * 2-byte letters in host memory takes 0.21-0.22 ms of host time with 324 bytes
+ * staged, against 10.36 ms with all 524,464,975 before; 4-byte letters 0.20 ms
+ * with 322 bytes against 5.50 ms. */
 int huff_wdecompress_range(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_t first, uint64_t count,
                            void* out, size_t cap_letters);
 /* self-synchronising decode of a device stream (no index), d_comp at any
@@ -220,6 +287,10 @@ uint64_t huff_diag_wide_index_form_launches(uint32_t i);
 uint32_t huff_diag_wrange_builds(void);
 const char* huff_diag_wrange_build_name(uint32_t i);
 uint64_t huff_diag_wrange_build_launches(uint32_t i);
+/* the compressed bytes huff_wdecompress_range has copied to the device for its
+ * indexed route, by this process so far (huff_diag_range_staged_bytes counts
+ * the byte path's, and only those) */
+uint64_t huff_diag_wrange_staged_bytes(void);
 /* The geometry of a tree's device tables, computed on the host (no context,
  * no GPU): the facts the launchers select a build by, not the build.
  * out[0] letter width in bytes          out[8]  deepest code (decoder tables)
