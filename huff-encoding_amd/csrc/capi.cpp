@@ -243,11 +243,38 @@ uint64_t huff_tree_root_weight(const huff_tree* t) { return t ? t->t.root_weight
 
 int huff_tree_read_codes(const huff_tree* t, uint64_t code[256], uint8_t len[256]) {
     if (!t || !code || !len) return fail(HUFF_E_INVALID_ARG, "null argument");
-    const huff::EncTables& e = t->enc_tables();
-    std::memcpy(code, e.code, sizeof(e.code));
-    std::memcpy(len, e.len, sizeof(e.len));
-    if (!e.fits64) return fail(HUFF_E_CODE_TOO_LONG, "a code is longer than 64 bits; use huff_tree_code_bits");
-    return HUFF_OK;
+    return guarded([&]() -> huff::Status {
+        const huff::EncTables* e = nullptr;
+        const huff::Status st = t->enc_tables(&e);
+        if (st) {  // past 255 bits: no table (lengths are 8 bits wide)
+            std::memset(code, 0, 256 * sizeof(uint64_t));
+            std::memset(len, 0, 256);
+            return st;
+        }
+        std::memcpy(code, e->code, sizeof(e->code));
+        std::memcpy(len, e->len, sizeof(e->len));
+        if (!e->fits64)
+            return huff::Status::err(HUFF_E_CODE_TOO_LONG, "a code is longer than 64 bits; use huff_tree_code_bits");
+        return huff::Status::ok();
+    });
+}
+
+int huff_tree_max_depth(const huff_tree* t, uint32_t* depth) {
+    if (!t || !depth) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        *depth = t->t.max_depth();
+        return huff::Status::ok();
+    });
+}
+
+int huff_tree_deep_words(const huff_tree* t, uint32_t words[2048]) {
+    if (!t || !words) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&]() -> huff::Status {
+        std::vector<uint32_t> w;
+        HUFF_TRY(huff::build_deep_words(t->t, w));
+        std::memcpy(words, w.data(), w.size() * 4);
+        return huff::Status::ok();
+    });
 }
 
 int huff_tree_code_bits(const huff_tree* t, uint8_t letter, uint8_t* bits, size_t cap, size_t* nbits) {
@@ -542,8 +569,9 @@ int huff_enc_pack_shards(huff_enc* e, const uint64_t* hists, uint32_t world, uin
         }
         auto t = std::make_unique<huff_tree>();
         HUFF_TRY(huff::HuffTree::from_weights(huff::shard_weights(hists, world), t->t));
-        const huff::EncTables& et = t->enc_tables();
-        const uint64_t base = huff::shard_bit_base(hists, rank, et.len);
+        const huff::EncTables* et = nullptr;
+        HUFF_TRY(t->enc_tables(&et));
+        const uint64_t base = huff::shard_bit_base(hists, rank, et->len);
         uint8_t prev[8];
         size_t np = 0;
         if (rank) huff::shard_prev_tail(tails, tail_lens, rank, prev, &np);

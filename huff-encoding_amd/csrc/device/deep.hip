@@ -20,6 +20,16 @@
 // Two small helpers of the file path's windowed decode live here too, as they
 // walk codes of any length: k_walk_end (the end of a window's last complete
 // code) and k_shift_bits (realign a window that starts inside a byte).
+//
+// The domain ends at 255 bits (huff::kMaxCodeLen): a table entry keeps its
+// code's length in 8 bits and a letter's code has kDeepWords = 8 words. A
+// try_from_bin tree may be deeper (duplicate letters); the host refuses it
+// with HUFF_E_CODE_TOO_LONG before any of these kernels is launched
+// (code_depth_ok, build_dec_tables), so no entry here has length 0 and the
+// walks below always advance. A chunk holds up to 65536 * 255 bits, so 1,024
+// of them pass 2^32: the chunk scan before k_pack_deep runs with 64-bit tile
+// sums (launch_scan's wide_tiles). tests/test_gpu_deep_ladder.py walks depths
+// 58 ... 255.
 #include "bitreader.hpp"
 
 namespace huff::dev {

@@ -330,6 +330,10 @@ __global__ __launch_bounds__(256) void k_chunk_bits(const uint32_t* __restrict__
 // start[c] = base + sum_{c' < c} bits[c'], start[nchunks] = total end, in two
 // launches over tiles of 1024 chunks. A chunk has at most 65536 * 57 bits <
 // 2^22, so a tile's local prefix sums fit 32 bits and scan with DPP.
+// The bound: every entry below 2^22, so that 1,024 of them stay below 2^32.
+// It holds for codes of at most kLongMaxLen = 57 bits (and for the other
+// callers' letter counts per segment); the deep encoder's chunks, up to
+// 65536 * 255 bits < 2^24, take k_scan_tiles_wide (launch_scan's wide_tiles).
 // k_scan_tiles: tile-local exclusive prefix -> start[], tile total -> tsum[].
 __global__ __launch_bounds__(1024) void k_scan_tiles(const uint64_t* __restrict__ bits, uint32_t nchunks,
                                                      uint64_t* __restrict__ start, uint64_t* __restrict__ tsum) {
@@ -347,6 +351,27 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(const uint64_t* __restrict_
         tot += wsum[w];
     }
     if (i < nchunks) start[i] = pre + incl - v;
+    if (t == 0) tsum[blockIdx.x] = tot;
+}
+
+// k_scan_tiles for entries below 2^26 (deep.hip's chunks): a wave's 64 entries
+// still scan in 32 bits (< 2^32), the 16 wave totals add up in 64
+__global__ __launch_bounds__(1024) void k_scan_tiles_wide(const uint64_t* __restrict__ bits, uint32_t nchunks,
+                                                          uint64_t* __restrict__ start, uint64_t* __restrict__ tsum) {
+    __shared__ uint32_t wsum[16];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t i = blockIdx.x * 1024 + t;
+    const uint32_t v = i < nchunks ? static_cast<uint32_t>(bits[i]) : 0u;
+    const uint32_t incl = wave_scan_incl(v);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint64_t pre = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; ++w) {
+        pre += (w < wave) ? wsum[w] : 0u;
+        tot += wsum[w];
+    }
+    if (i < nchunks) start[i] = pre + (incl - v);
     if (t == 0) tsum[blockIdx.x] = tot;
 }
 
@@ -490,9 +515,12 @@ hipError_t launch_chunk_bits(const uint32_t* chunk_hist, uint32_t nchunks, const
 }
 
 hipError_t launch_scan(const uint64_t* bits, uint32_t nchunks, uint64_t base, uint64_t* start, uint64_t* tsum,
-                       hipStream_t s, HistDone done) {
+                       hipStream_t s, HistDone done, bool wide_tiles) {
     const uint32_t tiles = nchunks ? (nchunks + 1023) / 1024 : 1;
-    launch_k(k_scan_tiles, dim3(tiles), dim3(1024), 0, s, bits, nchunks, start, tsum);
+    if (wide_tiles)
+        launch_k(k_scan_tiles_wide, dim3(tiles), dim3(1024), 0, s, bits, nchunks, start, tsum);
+    else
+        launch_k(k_scan_tiles, dim3(tiles), dim3(1024), 0, s, bits, nchunks, start, tsum);
     if (tiles <= 64) {
         launch_k(k_scan_fix_small, dim3(tiles), dim3(1024), 0, s, nchunks, base, tsum, start, done.host,
                            done.tag);

@@ -598,8 +598,11 @@ struct DeepPackArgs {
 hipError_t launch_chunk_bits(const uint32_t* chunk_hist, uint32_t nchunks, const CodeLens& len, uint64_t* bits,
                              hipStream_t s);
 // tsum: scratch of ceil(nchunks / 1024) (>= 1) u64
+// wide_tiles: a tile of 1,024 entries may sum to 2^32 or more (the deep
+// encoder's chunks, up to 65,536 * 255 bits each): tile sums in 64 bits. Each
+// entry itself stays below 2^26 either way.
 hipError_t launch_scan(const uint64_t* bits, uint32_t nchunks, uint64_t base, uint64_t* start, uint64_t* tsum,
-                       hipStream_t s, HistDone done = HistDone{});
+                       hipStream_t s, HistDone done = HistDone{}, bool wide_tiles = false);
 hipError_t launch_pack(bool long_codes, const PackArgs& a, hipStream_t s);
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
 hipError_t launch_decode_fixed(const DecodeArgs& a, hipStream_t s);

@@ -194,6 +194,11 @@ Status build_dec_tables(const HuffTree& t, bool l2_sparse, DecTables& out) {
     }
     uint32_t mind = 0, maxd = 0;  // maxd > kLongMaxLen: the deep kernels (deep.hip)
     t.depth_range(&mind, &maxd);
+    // an entry keeps its code's length in 8 bits: a longer code would read as
+    // a shorter one (256 as 0, on which the serial walk never advances)
+    if (maxd > kMaxCodeLen)
+        return Status::err(HUFF_E_CODE_TOO_LONG, "the tree's longest code has " + std::to_string(maxd) +
+                                                     " bits: the decode tables take at most 255");
     out.maxdepth = maxd;
     out.all8 = (mind == 8 && maxd == 8);
     out.bits = std::min<uint32_t>(maxd, kLutMaxBits - 1);  // 11 bits: 8 KiB of LDS

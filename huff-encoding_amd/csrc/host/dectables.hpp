@@ -44,7 +44,8 @@ struct DecTables {
     bool l2dense = false;
 };
 
-// l2_sparse: never the dense form of the level-2 table (l2dense stays false)
+// l2_sparse: never the dense form of the level-2 table (l2dense stays false).
+// HUFF_E_CODE_TOO_LONG, with no table filled, past kMaxCodeLen bits.
 Status build_dec_tables(const HuffTree& t, bool l2_sparse, DecTables& out);
 
 }  // namespace huff

@@ -80,6 +80,8 @@ public:
     // semantics: a later leaf in left-to-right order wins). len 0 = absent.
     void read_codes(std::array<std::vector<uint8_t>, 256>& codes) const;
     // Right-aligned u64 codes; false if any code is longer than 64 bits.
+    // *maxlen = the longest code of any length. Past kMaxCodeLen bits a
+    // length no longer fits len[]: code[] and len[] are then all zero.
     bool read_codes_u64(uint64_t code[256], uint8_t len[256], uint32_t* maxlen) const;
     // Every leaf with its path (decode tables are built from these).
     std::vector<LeafCode> leaves() const;
@@ -97,6 +99,22 @@ private:
     std::vector<HuffNode> nodes_;
     int32_t root_ = -1;
 };
+
+// The depth limit of every fixed-width table (include/huffgpu.h, "Code
+// length"): lengths are kept in 8 bits (EncTables::len, the decode tables'
+// entries) and a deep code in kDeepWords 32-bit words. Parsing, as_bin,
+// num_leaves, max_depth and read_codes are exact for a tree of any size.
+constexpr uint32_t kMaxCodeLen = 255;
+constexpr uint32_t kDeepWords = 8;  // = dev::kDeepWords
+static_assert(kDeepWords * 32 >= kMaxCodeLen, "a code of kMaxCodeLen bits fits its words");
+
+// HUFF_E_CODE_TOO_LONG for a tree whose longest code exceeds kMaxCodeLen bits:
+// asked before any table of the tree is filled and before any launch.
+Status code_depth_ok(const HuffTree& t);
+// The deep encoder's code table (deep.hip): words[b * kDeepWords + q] = code
+// bits [32q, 32q + 32) of letter b, left-aligned, zero past the code and for
+// an absent letter. code_depth_ok's status, with `words` left empty.
+Status build_deep_words(const HuffTree& t, std::vector<uint32_t>& words);
 
 // ---------------------------------------------------------------------------
 // Sharded encode: shard `rank` of `world` contiguous shards.

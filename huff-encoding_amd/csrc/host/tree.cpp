@@ -202,28 +202,45 @@ bool HuffTree::read_codes_u64(uint64_t code[256], uint8_t len[256], uint32_t* ma
         if (maxlen) *maxlen = 1;
         return true;
     }
+    // try_from_bin takes a tree of any size (duplicate letters allow more
+    // than 256 leaves), so a length may not fit len[]: such a tree gets no
+    // table at all, only its true depth (the callers refuse it, code_depth_ok)
+    uint32_t too_deep = 0;
     struct Frame {
         int32_t node;
         uint32_t depth;
         uint64_t code;  // low 64 bits of the path (exact while depth <= 64)
     };
-    Frame st[512];
-    int sp = 0;
-    st[sp++] = {nodes_[root_].right, 1, 1};
-    st[sp++] = {nodes_[root_].left, 1, 0};
-    while (sp) {
-        const Frame fr = st[--sp];
+    std::vector<Frame> st;  // one entry per level of a left-leaning chain: no fixed bound
+    st.reserve(64);
+    st.push_back({nodes_[root_].right, 1, 1});
+    st.push_back({nodes_[root_].left, 1, 0});
+    while (!st.empty()) {
+        const Frame fr = st.back();
+        st.pop_back();
         const HuffNode& nd = nodes_[fr.node];
         if (nd.is_leaf) {
+            if (fr.depth > kMaxCodeLen) {
+                too_deep = std::max(too_deep, fr.depth);
+                continue;
+            }
             const uint8_t l = nd.letter;
             seen[l] = true;
             true_len[l] = fr.depth;
             code[l] = fr.depth <= 64 ? fr.code : 0;  // longer codes: read_codes (bit vectors)
-            len[l] = static_cast<uint8_t>(fr.depth);  // <= 255 (a 256-leaf tree's depth)
+            len[l] = static_cast<uint8_t>(fr.depth);
             continue;
         }
-        st[sp++] = {nd.right, fr.depth + 1, (fr.code << 1) | 1};
-        st[sp++] = {nd.left, fr.depth + 1, fr.code << 1};
+        st.push_back({nd.right, fr.depth + 1, (fr.code << 1) | 1});
+        st.push_back({nd.left, fr.depth + 1, fr.code << 1});
+    }
+    if (too_deep) {
+        for (int b = 0; b < 256; ++b) {
+            code[b] = 0;
+            len[b] = 0;
+        }
+        if (maxlen) *maxlen = too_deep;
+        return false;
     }
     uint32_t ml = 0;
     bool ok = true;
@@ -234,6 +251,25 @@ bool HuffTree::read_codes_u64(uint64_t code[256], uint8_t len[256], uint32_t* ma
     }
     if (maxlen) *maxlen = ml;
     return ok;
+}
+
+Status code_depth_ok(const HuffTree& t) {
+    const uint32_t d = t.max_depth();
+    if (d <= kMaxCodeLen) return Status::ok();
+    return Status::err(HUFF_E_CODE_TOO_LONG, "the tree's longest code has " + std::to_string(d) +
+                                                 " bits: the code tables take at most 255");
+}
+
+Status build_deep_words(const HuffTree& t, std::vector<uint32_t>& words) {
+    words.clear();
+    HUFF_TRY(code_depth_ok(t));
+    std::array<std::vector<uint8_t>, 256> bits;
+    t.read_codes(bits);
+    words.assign(256 * kDeepWords, 0);
+    for (int b = 0; b < 256; ++b)
+        for (size_t k = 0; k < bits[b].size(); ++k)
+            if (bits[b][k]) words[b * kDeepWords + k / 32] |= 0x80000000u >> (k % 32);
+    return Status::ok();
 }
 
 size_t HuffTree::num_leaves() const {

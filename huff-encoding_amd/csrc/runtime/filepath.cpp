@@ -428,7 +428,9 @@ static Status file_compress_impl(huff_ctx* ctx, const char* src, const char* dst
     for (size_t i = np >= 2 ? np - 2 : 0; i < np; ++i) HUFF_TRY(merge(i));
     auto tree = std::make_unique<huff_tree>();
     HUFF_TRY(HuffTree::from_weights(bw, tree->t));
-    const EncTables& et = tree->enc_tables();
+    const EncTables* etp = nullptr;
+    HUFF_TRY(tree->enc_tables(&etp));
+    const EncTables& et = *etp;
 
     // header
     std::vector<uint8_t> tbits = tree->t.as_bin();
@@ -553,6 +555,7 @@ static Status file_decompress_impl(huff_ctx* ctx, const char* src, const char* d
     auto tree = std::make_unique<huff_tree>();
     if (HuffTree::try_from_bin(unpack_msb0(tb.data(), nbits), tree->t))
         return Status::err(HUFF_E_INVALID_HEADER, q + " stores invalid header information");
+    HUFF_TRY(code_depth_ok(tree->t));  // before the output file exists and before any launch
     const size_t plen = total - 5 - tree_len;
     File out;
     {

@@ -27,6 +27,7 @@ Status IndexlessStep::open(huff_ctx* c, const huff_tree* t, const uint8_t* d_com
                            uint64_t valid_bits) {
     ctx = c;
     tree = t;
+    HUFF_TRY(t->dec_tables(&dt));  // HUFF_E_CODE_TOO_LONG past kMaxCodeLen bits: before the stream is touched
     HUFF_TRY(ctx->activate());
     HUFF_TRY(ctx->aligned_stream(&d_comp, comp_bytes));
     a = dev::IndexlessArgs{};

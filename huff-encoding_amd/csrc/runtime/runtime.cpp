@@ -27,6 +27,7 @@ static_assert(huff::kLutMaxBits == huff::dev::kLutMaxBits, "host/dectables.hpp m
 static_assert(huff::kSsMaxBits == huff::dev::kSsMaxBits, "host/dectables.hpp mirrors dev::kSsMaxBits");
 static_assert(huff::kSsSlow == huff::dev::kSsSlow, "host/dectables.hpp mirrors dev::kSsSlow");
 static_assert(huff::kLongMaxLen == huff::dev::kLongMaxLen, "host/dectables.hpp mirrors dev::kLongMaxLen");
+static_assert(huff::kDeepWords == huff::dev::kDeepWords, "host/huff_coding.hpp mirrors dev::kDeepWords");
 
 #define HIP_TRY(expr) HIP_TRY_RT(expr)
 
@@ -35,22 +36,17 @@ static_assert(huff::kLongMaxLen == huff::dev::kLongMaxLen, "host/dectables.hpp m
 // ---------------------------------------------------------------------------
 huff_tree::huff_tree() : id(g_tree_ids.fetch_add(1)) {}
 
-const huff::EncTables& huff_tree::enc_tables() const {
+huff::Status huff_tree::enc_tables(const huff::EncTables** out) const {
     std::lock_guard<std::mutex> g(m);
     if (!enc) {
         auto e = std::make_unique<huff::EncTables>();
         e->fits64 = t.read_codes_u64(e->code, e->len, &e->maxlen);
-        if (e->maxlen > huff::dev::kLongMaxLen) {  // deep codes: left-aligned words (deep.hip)
-            std::array<std::vector<uint8_t>, 256> bits;
-            t.read_codes(bits);
-            e->deep.assign(256 * huff::dev::kDeepWords, 0);
-            for (int b = 0; b < 256; ++b)
-                for (size_t k = 0; k < bits[b].size(); ++k)
-                    if (bits[b][k]) e->deep[b * huff::dev::kDeepWords + k / 32] |= 0x80000000u >> (k % 32);
-        }
+        if (e->maxlen > huff::dev::kLongMaxLen)  // deep codes: left-aligned words (deep.hip), at most kMaxCodeLen bits
+            HUFF_TRY(huff::build_deep_words(t, e->deep));
         enc = std::move(e);
     }
-    return *enc;
+    *out = enc.get();
+    return huff::Status::ok();
 }
 
 huff::Status huff_tree::dec_tables(const huff::DecTables** out) const {
@@ -529,7 +525,9 @@ huff::Status huff_enc::hist_row(long long* d_row) {
 huff::Status huff_enc::bits(const huff_tree* t, uint64_t* total) {
     HUFF_TRY(encode_guard());
     if (!have_hist) return huff::Status::err(HUFF_E_STATE, "huff_enc_hist must run before bits/pack");
-    const huff::EncTables& et = t->enc_tables();
+    const huff::EncTables* etp = nullptr;
+    HUFF_TRY(t->enc_tables(&etp));
+    const huff::EncTables& et = *etp;
     uint64_t b = 0;
     for (int i = 0; i < 256; ++i) {
         if (w[i] && et.len[i] == 0) {
@@ -601,7 +599,9 @@ huff::Status huff_enc::pack(const huff_tree* t, uint64_t base, const uint8_t* pr
         HIP_TRY(huff::dev::launch_task_sums(d_in, n, static_cast<uint64_t*>(task_sums.p), s));
         sums_valid = true;
     }
-    const huff::EncTables& et = t->enc_tables();
+    const huff::EncTables* etp = nullptr;
+    HUFF_TRY(t->enc_tables(&etp));  // (bits() above has refused a tree past kMaxCodeLen bits)
+    const huff::EncTables& et = *etp;
     const bool long_codes = et.maxlen > huff::dev::kShortMaxLen;
     if ((base & 7) == 0 && et.maxlen == 8 && !huff::fixed8_disabled()) {
         bool all8 = true;
@@ -628,8 +628,10 @@ huff::Status huff_enc::pack(const huff_tree* t, uint64_t base, const uint8_t* pr
                                             static_cast<uint64_t*>(chunk_bits.p), s);
     }));
     HUFF_TRY(ctx->timed("scan", [&] {
+        // past kLongMaxLen bits a tile of 1,024 chunks can hold 2^32 bits: the 64-bit tile sums
         return huff::dev::launch_scan(static_cast<const uint64_t*>(chunk_bits.p), nchunks, base & 7,
-                                      static_cast<uint64_t*>(chunk_start.p), static_cast<uint64_t*>(tsum.p), s);
+                                      static_cast<uint64_t*>(chunk_start.p), static_cast<uint64_t*>(tsum.p), s,
+                                      huff::dev::HistDone{}, et.maxlen > huff::dev::kLongMaxLen);
     }));
     if (et.maxlen > huff::dev::kLongMaxLen) {  // deep codes (deep.hip): ORed into a zeroed output
         const uint64_t nb = ((base & 7) + tb + 7) / 8;
@@ -735,14 +737,14 @@ huff::Status huff_enc::expand_index() {
 
 huff::Status huff_enc::decode(const huff_tree* t, const uint8_t* d_comp, uint64_t comp_bytes, uint8_t* d_out) {
     if (!packed) return huff::Status::err(HUFF_E_STATE, "no restart index: pack (or upload an index) first");
+    const huff::DecTables* dt = nullptr;
+    HUFF_TRY(t->dec_tables(&dt));  // first: HUFF_E_CODE_TOO_LONG past kMaxCodeLen bits
     if (!codes_match(t))
         return huff::Status::err(HUFF_E_STATE, "decode tree differs from the tree the stream was packed (or its index "
                                                "uploaded) with");
     if (reinterpret_cast<uintptr_t>(d_comp) & 3)
         return huff::Status::err(HUFF_E_INVALID_ARG, "compressed stream must be 4-byte aligned");
     HUFF_TRY(ctx->activate());
-    const huff::DecTables* dt = nullptr;
-    HUFF_TRY(t->dec_tables(&dt));
     if (dt->all8 && (bit_base & 7) == 0 && !huff::fixed8_disabled()) {  // inverse byte substitution
         huff::dev::BytemapArgs m{};
         m.src = d_comp;
@@ -814,13 +816,13 @@ huff::Status huff_enc::decode_ranges(const huff_tree* t, const uint8_t* d_comp, 
                                      const uint64_t* first, const uint64_t* count, const uint64_t* out_begin,
                                      uint32_t nreq, uint8_t* d_out, size_t out_cap, uint32_t* status) {
     if (!packed) return huff::Status::err(HUFF_E_STATE, "no restart index: pack (or upload an index) first");
+    const huff::DecTables* dt = nullptr;
+    HUFF_TRY(t->dec_tables(&dt));  // first: HUFF_E_CODE_TOO_LONG past kMaxCodeLen bits
     if (!codes_match(t))
         return huff::Status::err(HUFF_E_STATE, "decode tree differs from the tree the stream was packed (or its index "
                                                "uploaded) with");
     if (reinterpret_cast<uintptr_t>(d_comp) & 3)
         return huff::Status::err(HUFF_E_INVALID_ARG, "compressed stream must be 4-byte aligned");
-    const huff::DecTables* dt = nullptr;
-    HUFF_TRY(t->dec_tables(&dt));
     if (dt->maxdepth > huff::dev::kLongMaxLen)
         return huff::Status::err(HUFF_E_CODE_TOO_LONG, "letter ranges need codes of at most 57 bits: decode the "
                                                        "stream whole (huff_enc_decode)");
@@ -907,18 +909,20 @@ huff::Status huff_enc::upload_index(const huff_index_host& idx) {
 }
 
 void huff_enc::remember_tree(const huff_tree* t) {
-    const huff::EncTables& et = t->enc_tables();
-    std::memcpy(packed_len, et.len, sizeof packed_len);
-    std::memcpy(packed_code, et.code, sizeof packed_code);
-    packed_deep = et.deep;
+    const huff::EncTables* et = nullptr;
+    if (t->enc_tables(&et)) return;  // not reached: pack took these tables
+    std::memcpy(packed_len, et->len, sizeof packed_len);
+    std::memcpy(packed_code, et->code, sizeof packed_code);
+    packed_deep = et->deep;
     packed_any_tree = false;
 }
 
 bool huff_enc::codes_match(const huff_tree* t) const {
     if (packed_any_tree) return true;
-    const huff::EncTables& et = t->enc_tables();
-    return std::memcmp(packed_len, et.len, sizeof packed_len) == 0 &&
-           std::memcmp(packed_code, et.code, sizeof packed_code) == 0 && packed_deep == et.deep;
+    const huff::EncTables* et = nullptr;
+    if (t->enc_tables(&et)) return false;  // not reached: the decodes ask for the decode tables first
+    return std::memcmp(packed_len, et->len, sizeof packed_len) == 0 &&
+           std::memcmp(packed_code, et->code, sizeof packed_code) == 0 && packed_deep == et->deep;
 }
 
 // ---------------------------------------------------------------------------
@@ -986,6 +990,10 @@ Status weights_threaded_from_host(huff_ctx* ctx, const uint8_t* bytes, size_t n,
 Status compress_host(huff_ctx* ctx, const uint8_t* bytes, size_t n, const huff_tree* t, huff_compress_data** out) {
     *out = nullptr;
     if (n == 0) return Status::err(HUFF_E_EMPTY_COMP, "provided comp_bytes are empty");
+    if (t) {  // HUFF_E_CODE_TOO_LONG past kMaxCodeLen bits, before anything is staged or launched
+        const EncTables* et = nullptr;
+        HUFF_TRY(t->enc_tables(&et));
+    }
     HUFF_TRY(stage_input(ctx, bytes, n));
     huff_enc e;
     HUFF_TRY(e.init(ctx, static_cast<const uint8_t*>(ctx->d_in.p), n));
@@ -1018,6 +1026,8 @@ Status compress_host(huff_ctx* ctx, const uint8_t* bytes, size_t n, const huff_t
 }
 
 Status decompress_host(huff_ctx* ctx, const huff_compress_data* cd, uint8_t* out, size_t cap, size_t* out_len) {
+    const DecTables* dt = nullptr;
+    HUFF_TRY(cd->tree->dec_tables(&dt));  // HUFF_E_CODE_TOO_LONG past kMaxCodeLen bits, before anything is staged
     if (!cd->index) {
         // comp.rs:513-516: all bytes but the last give 8 bits, the last 8 - padding
         const uint64_t valid = static_cast<uint64_t>(cd->comp.size()) * 8 - cd->padding;

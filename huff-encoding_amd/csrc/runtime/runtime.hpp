@@ -78,7 +78,8 @@ struct huff_tree {
     mutable std::vector<int32_t> up;  // parent links for branch codes (capi_util.hpp parent_links), built once
 
     huff_tree();
-    const huff::EncTables& enc_tables() const;
+    // both: HUFF_E_CODE_TOO_LONG, with nothing built, past huff::kMaxCodeLen bits
+    huff::Status enc_tables(const huff::EncTables** out) const;
     huff::Status dec_tables(const huff::DecTables** out) const;
 };
 

@@ -524,6 +524,110 @@ static void dec_tables_fibonacci() {
     CHECK(f.chain == (d.maxdepth - d.bits + 7) / 8 && f.chain >= 6);
 }
 
+// Chain trees as try_from_bin takes them, 2 ... 5,000 leaves, leaning either
+// way, letters repeating past 256 leaves: the shape and the bit-vector codes
+// are exact at any size; the fixed-width tables (u64 codes, the deep encoder's
+// words, the decode tables) exist up to kMaxCodeLen bits and are refused above
+// with nothing filled. A left chain puts one frame per level on a walk's stack.
+static void deep_chains() {
+    for (size_t n : {2u, 57u, 58u, 65u, 256u, 257u, 300u, 512u, 513u, 600u, 5000u}) {
+        for (int left = 0; left < 2; ++left) {
+            const int before = g_fail;
+            const uint32_t depth = static_cast<uint32_t>(n - 1);
+            // leaf k of the left-to-right order: its letter and its path
+            std::vector<uint8_t> letter(n);
+            std::vector<std::string> path(n);
+            for (size_t k = 0; k < n; ++k) {
+                letter[k] = static_cast<uint8_t>(k * 37 + 11);
+                if (left) path[k] = k == 0 ? std::string(n - 1, '0') : std::string(n - 1 - k, '0') + "1";
+                else path[k] = std::string(k, '1') + (k + 1 < n ? "0" : "");
+            }
+            std::vector<uint8_t> bits;
+            auto put_leaf = [&](size_t k) {
+                bits.push_back(0);
+                for (int b = 7; b >= 0; --b) bits.push_back((letter[k] >> b) & 1);
+            };
+            if (left) bits.assign(n - 1, 1);
+            for (size_t k = 0; k < n; ++k) {
+                if (!left && k + 1 < n) bits.push_back(1);
+                put_leaf(k);
+            }
+            std::string want[256];  // a later leaf wins
+            for (size_t k = 0; k < n; ++k) want[letter[k]] = path[k];
+
+            HuffTree t;
+            CHECK(!HuffTree::try_from_bin(bits, t));
+            CHECK(t.as_bin() == bits);
+            CHECK(t.num_leaves() == n && t.max_depth() == depth);
+            const std::vector<LeafCode> lv = t.leaves();
+            CHECK(lv.size() == n);
+            int bad = 0;
+            for (size_t k = 0; k < n && k < lv.size(); ++k)
+                bad += lv[k].letter != letter[k] || lv[k].len != path[k].size() || lv[k].bits.size() != path[k].size();
+            CHECK(bad == 0);
+            std::array<std::vector<uint8_t>, 256> codes;
+            t.read_codes(codes);
+            bad = 0;
+            for (int b = 0; b < 256; ++b) {
+                std::string s;
+                for (uint8_t x : codes[b]) s.push_back(x ? '1' : '0');
+                bad += s != want[b];
+            }
+            CHECK(bad == 0);
+
+            // through a container
+            const uint8_t payload[3] = {0xA5, 0x00, 0xFF};
+            std::vector<uint8_t> blob;
+            CHECK(!container_bits_to_bytes(bits, payload, 3, 5, blob));
+            HuffTree t2;
+            uint8_t pad = 0;
+            size_t off = 0, len = 0;
+            CHECK(!container_from_bytes(blob.data(), blob.size(), t2, pad, off, len));
+            CHECK(t2.as_bin() == bits && pad == 5 && len == 3 && off + len == blob.size());
+            CHECK(t2.max_depth() == depth && t2.num_leaves() == n);
+
+            // the fixed-width tables
+            uint64_t code[256];
+            uint8_t clen[256];
+            uint32_t maxlen = 0;
+            std::memset(code, 0xEE, sizeof code);
+            std::memset(clen, 0xEE, sizeof clen);
+            const bool fits = t.read_codes_u64(code, clen, &maxlen);
+            std::vector<uint32_t> words(7, 1u);
+            DecTables d;
+            d.lut.assign(3, 9u);
+            CHECK(maxlen == depth && fits == (depth <= 64));
+            bad = 0;
+            if (depth <= kMaxCodeLen) {
+                CHECK(!code_depth_ok(t));
+                CHECK(!build_deep_words(t, words));
+                CHECK(words.size() == 256 * kDeepWords);
+                for (int b = 0; b < 256 && words.size() == 256 * kDeepWords; ++b) {
+                    const std::string& s = want[b];
+                    bad += clen[b] != s.size();
+                    uint64_t c = 0;
+                    if (s.size() <= 64)
+                        for (char ch : s) c = (c << 1) | (ch == '1');
+                    bad += code[b] != c;
+                    for (uint32_t k = 0; k < 32 * kDeepWords; ++k) {
+                        const uint32_t bit = (words[b * kDeepWords + k / 32] >> (31 - k % 32)) & 1u;
+                        bad += bit != (k < s.size() && s[k] == '1');
+                    }
+                }
+                CHECK(!build_dec_tables(t, false, d));
+                check_dec_tables(left ? "left chain" : "right chain", t, d);
+            } else {
+                CHECK(code_depth_ok(t).code == HUFF_E_CODE_TOO_LONG);
+                CHECK(build_deep_words(t, words).code == HUFF_E_CODE_TOO_LONG && words.empty());
+                for (int b = 0; b < 256; ++b) bad += clen[b] != 0 || code[b] != 0;
+                CHECK(build_dec_tables(t, false, d).code == HUFF_E_CODE_TOO_LONG && d.lut.empty());
+            }
+            CHECK(bad == 0);
+            if (g_fail != before) std::printf("  ^ chain of %zu leaves, leaning %s\n", n, left ? "left" : "right");
+        }
+    }
+}
+
 // huff_batch_seg_entries' layout (host/batch_container.hpp): every stream's
 // segments fit between its offset and the next stream's, and the last stream's
 // below the total, for stream sizes of every shape
@@ -568,6 +672,7 @@ int main() {
     dec_tables_l2_fits_neither();
     dec_tables_depth_33();
     dec_tables_fibonacci();
+    deep_chains();
     shard_plan_matches_single_stream();
     tree_normal_init();
     tree_single_branch();

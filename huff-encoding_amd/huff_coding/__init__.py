@@ -108,6 +108,9 @@ def _check(rc: int):
     raise HuffError(rc, msg)
 
 
+_BIT_CHARS = bytes.maketrans(b"\x00\x01", b"01")
+
+
 def _buf(data) -> Tuple[object, int, int]:
     """(keepalive, address, length) of a bytes-like or uint8 array"""
     if isinstance(data, np.ndarray):
@@ -297,13 +300,28 @@ class HuffTree:
         """tree_inner.rs:356-419 -> {byte: '0101'}"""
         out = {}
         L = load()
-        bits = (C.c_uint8 * 512)()
+        cap = max(512, self.max_depth())  # a try_from_bin tree may be deeper than any 256-leaf tree
+        bits = (C.c_uint8 * cap)()
         n = C.c_size_t()
         for b in range(256):
-            _check(L.huff_tree_code_bits(self.h, b, bits, 512, C.byref(n)))
+            _check(L.huff_tree_code_bits(self.h, b, bits, cap, C.byref(n)))
             if n.value:
-                out[b] = "".join(str(bits[k]) for k in range(n.value))
+                out[b] = bytes(bits[: n.value]).translate(_BIT_CHARS).decode()
         return out
+
+    def max_depth(self) -> int:
+        """the longest code's bits, whatever the tree's size (huff_tree_max_depth)"""
+        d = C.c_uint32()
+        _check(load().huff_tree_max_depth(self.h, C.byref(d)))
+        return int(d.value)
+
+    def deep_words(self) -> np.ndarray:
+        """uint32[256, 8]: every code left-aligned, its first bit in bit 31 of
+        word 0 (huff_tree_deep_words: the table the encoder of codes past 57
+        bits reads). HuffError(CODE_TOO_LONG) past 255 bits."""
+        w = np.zeros((256, 8), np.uint32)
+        _check(load().huff_tree_deep_words(self.h, w.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return w
 
     def code_table(self):
         """(u64 code right-aligned, u8 len) per byte"""
@@ -316,8 +334,14 @@ class HuffTree:
     def as_bin(self) -> str:
         """tree_inner.rs:632-668 as a '0'/'1' string"""
         n = C.c_size_t()
-        buf = (C.c_uint8 * 512)()
-        _check(load().huff_tree_as_bin(self.h, buf, 512, C.byref(n)))
+        cap = 512  # a 256-leaf tree takes 320 bytes; a larger try_from_bin tree is read again at its size
+        buf = (C.c_uint8 * cap)()
+        rc = load().huff_tree_as_bin(self.h, buf, cap, C.byref(n))
+        if rc == _lib.E_BUFFER_TOO_SMALL:
+            cap = (n.value + 7) // 8
+            buf = (C.c_uint8 * cap)()
+            rc = load().huff_tree_as_bin(self.h, buf, cap, C.byref(n))
+        _check(rc)
         return "".join("1" if (buf[k // 8] >> (7 - k % 8)) & 1 else "0" for k in range(n.value))
 
     def num_leaves(self) -> int:

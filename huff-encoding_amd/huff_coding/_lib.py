@@ -73,6 +73,8 @@ SIGNATURES = [
     ("huff_tree_num_leaves", sz, [vp]),
     ("huff_tree_root_weight", C.c_uint64, [vp]),
     ("huff_tree_read_codes", i, [vp, u64p, u8p]),
+    ("huff_tree_max_depth", i, [vp, C.POINTER(C.c_uint32)]),
+    ("huff_tree_deep_words", i, [vp, C.POINTER(C.c_uint32)]),
     ("huff_tree_code_bits", i, [vp, C.c_uint8, u8p, sz, szp]),
     ("huff_tree_as_bin", i, [vp, u8p, sz, szp]),
     ("huff_tree_try_from_bin", i, [vp, sz, C.POINTER(vp)]),

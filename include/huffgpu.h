@@ -44,7 +44,7 @@ enum huff_status {
     HUFF_E_BUFFER_TOO_SMALL = 6,/* caller buffer too small; *_len outputs hold the need   */
     HUFF_E_CODE_TOO_LONG = 7,   /* a code too long for the requested view (u64 code table, */
                                 /* wide letters' kernels); byte-path compress/decompress  */
-                                /* take any length (deep.hip)                             */
+                                /* take up to 255 bits (deep.hip; "Code length" below)    */
     HUFF_E_HIP = 8,             /* HIP runtime error (message has the HIP error string)   */
     HUFF_E_IO = 9,              /* ErrorKind::Io huff/src/error.rs                         */
     HUFF_E_UNRECOGNIZED = 10,   /* ErrorKind::UnrecognizedFormat                           */
@@ -123,10 +123,32 @@ int huff_tree_clone(const huff_tree* t, huff_tree** out);
 void huff_tree_free(huff_tree* t);
 size_t huff_tree_num_leaves(const huff_tree* t);
 uint64_t huff_tree_root_weight(const huff_tree* t);
+/* Code length. The reference's codes are unbounded bit vectors, and
+ * huff_tree_try_from_bin takes a tree of any size (duplicate letters allow
+ * more than 256 leaves, so a code may be longer than a 256-leaf tree's 255
+ * bits). Parsing, huff_tree_as_bin, huff_tree_num_leaves, huff_tree_max_depth,
+ * huff_tree_code_bits and the branch accessors are exact for every such tree.
+ * Everything that needs fixed-width tables keeps a length in 8 bits and a code
+ * in eight 32-bit words, and returns HUFF_E_CODE_TOO_LONG when the longest
+ * code exceeds 255 bits: huff_tree_read_codes, huff_tree_deep_words,
+ * huff_compress_with_tree, huff_decompress, huff_decompress_range,
+ * huff_dev_decompress, huff_enc_bits / pack / decode / decode_ranges,
+ * huff_enc_from_stream / from_indexed_stream, huff_cd_build_index /
+ * attach_index and huff_file_decompress. The status comes back before any
+ * table is filled, before anything is staged and before any launch. */
 /* read_codes (tree_inner.rs:356-419): right-aligned code and bit length per
  * byte, len 0 = no code. HUFF_E_CODE_TOO_LONG if a code exceeds 64 bits (use
- * huff_tree_code_bits then). */
+ * huff_tree_code_bits then); code[] and len[] are all zero when one exceeds
+ * 255 bits. */
 int huff_tree_read_codes(const huff_tree* t, uint64_t code[256], uint8_t len[256]);
+/* the longest code's bits (a single-leaf tree: 1), whatever the tree's size */
+int huff_tree_max_depth(const huff_tree* t, uint32_t* depth);
+/* The code table the encoder of codes longer than 57 bits reads (deep.hip):
+ * words[b * 8 + q] = code bits [32q, 32q + 32) of byte b, the first bit in
+ * bit 31, zero past the code and for a byte without one; the later leaf of a
+ * duplicated letter wins, as in read_codes. HUFF_E_CODE_TOO_LONG past 255
+ * bits, words untouched. */
+int huff_tree_deep_words(const huff_tree* t, uint32_t words[2048]);
 /* one code as a bit string (one bit per byte), any length */
 int huff_tree_code_bits(const huff_tree* t, uint8_t letter, uint8_t* bits, size_t cap, size_t* nbits);
 /* as_bin (tree_inner.rs:632-668): packed Msb0 bytes with zero tail bits. */
