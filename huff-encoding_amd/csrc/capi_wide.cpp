@@ -394,6 +394,70 @@ int huff_dev_wdecompress(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_co
     });
 }
 
+int huff_dev_wweights_map(huff_ctx* ctx, uint32_t width, const void* d_letters, size_t n, void* letters_out,
+                          uint64_t* weights_out, size_t cap, size_t* count) {
+    if (!ctx || !count || (n && !d_letters)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        std::vector<uint8_t> u;
+        std::vector<uint64_t> c;
+        HUFF_TRY(huff::wweights_map_dev(ctx, width, static_cast<const uint8_t*>(d_letters), n, u, c));
+        *count = c.size();
+        if (cap < c.size()) return huff::Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+        if (letters_out && !u.empty()) std::memcpy(letters_out, u.data(), u.size());
+        if (weights_out && !c.empty()) std::memcpy(weights_out, c.data(), c.size() * 8);
+        return huff::Status::ok();
+    });
+}
+
+// many small wide-letter streams under one tree (runtime/wbatch_rt.cpp)
+static_assert(static_cast<int>(huff::dev::kBatchEmpty) == static_cast<int>(HUFF_E_EMPTY_COMP) &&
+                  static_cast<int>(huff::dev::kBatchInvalid) == static_cast<int>(HUFF_E_INVALID_ARG) &&
+                  static_cast<int>(huff::dev::kBatchMissing) == static_cast<int>(HUFF_E_MISSING_LETTER) &&
+                  static_cast<int>(huff::dev::kBatchCorrupt) == static_cast<int>(HUFF_E_CORRUPT),
+              "the kernels write the C ABI's status codes");
+
+int huff_wbatch_bits(huff_ctx* ctx, const huff_wtree* t, const void* d_in, const uint64_t* d_offsets, uint32_t nstreams,
+                     uint64_t* d_bits, uint64_t* d_comp_offsets, uint64_t* d_index_offsets, uint64_t* d_missing,
+                     uint32_t* d_status) {
+    if (!ctx || !t || !d_comp_offsets || !d_index_offsets ||
+        (nstreams && (!d_in || !d_offsets || !d_bits || !d_missing || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return huff::wbatch_bits(ctx, t, static_cast<const uint8_t*>(d_in), d_offsets, nstreams, d_bits, d_comp_offsets,
+                                 d_index_offsets, d_missing, d_status);
+    });
+}
+
+int huff_wbatch_pack(huff_ctx* ctx, const huff_wtree* t, const void* d_in, const uint64_t* d_offsets,
+                     const uint64_t* d_bits, const uint64_t* d_comp_offsets, const uint64_t* d_index_offsets,
+                     uint32_t* d_status, uint32_t nstreams, uint8_t* d_out, size_t out_cap, uint32_t* d_sub,
+                     size_t sub_cap) {
+    if (!ctx || !t || !d_comp_offsets || !d_index_offsets || (nstreams && (!d_offsets || !d_bits || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return huff::wbatch_pack(ctx, t, static_cast<const uint8_t*>(d_in), d_offsets, d_bits, d_comp_offsets,
+                                 d_index_offsets, d_status, nstreams, d_out, out_cap, d_sub, sub_cap);
+    });
+}
+
+int huff_wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                       const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_index_offsets,
+                       const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, void* d_out,
+                       uint32_t* d_status) {
+    if (!ctx || !t || (nstreams && (!d_comp_offsets || !d_bits || !d_index_offsets || !d_offsets || !d_status_in ||
+                                    !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (!d_sub) return fail(HUFF_E_INVALID_ARG, "a wide batch decodes through its restart index (d_sub)");
+    return guarded([&] {
+        return huff::wbatch_decode(ctx, t, d_comp, d_comp_offsets, d_bits, d_sub, d_index_offsets, d_offsets,
+                                   d_status_in, nstreams, static_cast<uint8_t*>(d_out), d_status);
+    });
+}
+
+uint32_t huff_diag_wbatch_builds(void) { return huff::dev::wbatch_builds(); }
+const char* huff_diag_wbatch_build_name(uint32_t i) { return huff::dev::wbatch_build_name(i); }
+uint64_t huff_diag_wbatch_build_launches(uint32_t i) { return huff::dev::wbatch_build_launches(i); }
+
 // diagnostics: which wide-letter build ran, from which restart form
 uint32_t huff_diag_wide_builds(void) { return huff::dev::wide_builds(); }
 const char* huff_diag_wide_build_name(uint32_t i) { return huff::dev::wide_build_name(i); }

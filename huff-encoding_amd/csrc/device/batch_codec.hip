@@ -525,6 +525,11 @@ hipError_t launch_batch_bits(const BatchBitsArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_batch_scan(const BatchBitsArgs& a, hipStream_t s) {
+    launch_k(k_batch_scan, dim3(1), dim3(kScanThreads), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_pack(const BatchPackArgs& a, hipStream_t s) {
     if (a.nstreams == 0) return hipSuccess;
     launch_k(k_batch_pack, dim3(a.nstreams), dim3(kBThreads), 0, s, a);

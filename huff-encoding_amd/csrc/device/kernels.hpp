@@ -677,6 +677,55 @@ hipError_t launch_wide_decode_ranges(const WRangesArgs& a, hipStream_t s);
 uint32_t wide_range_builds();
 const char* wide_range_build_name(uint32_t i);
 uint64_t wide_range_build_launches(uint32_t i);
+// compress_with_tree / decompress of a batch of many small wide-letter streams
+// under one tree (wbatch.hip; host/wbatch_plan.hpp). Stream s = the letters
+// [off[s], off[s + 1]) of `in` (a descending pair: empty), of t.width bytes
+// each; the layout of its compressed bytes and index entries is BatchPackArgs'.
+// One wave per stream, kWBatchWaves waves per persistent workgroup.
+constexpr uint32_t kBatchEmpty = 14;  // = HUFF_E_EMPTY_COMP (kBatchEmptyComp): a stream of no letters
+struct WBatchEncArgs {
+    WideArgs t;                   // the tree's table: width, table .. table_in_lds, cu_count, stage_words
+    const uint8_t* in;            // 16-B aligned
+    const uint64_t* off;          // [nstreams + 1], in letters
+    uint32_t nstreams;
+    uint64_t* bits;               // [nstreams]      (bits: written; pack: read)
+    const uint64_t* comp_off;     // [nstreams + 1]  (pack)
+    const uint64_t* idx_off;      // [nstreams + 1]  (pack)
+    unsigned long long* missing;  // [nstreams]      (bits): the first letter without a code, else ~0
+    uint32_t* status;             // [nstreams]      (bits: written; pack: read, kBatchInvalid set where
+                                  //                  the letters do not add up to bits[s])
+    uint8_t* out;                 // (pack) any alignment
+    uint32_t* sub;                // (pack) may be null: no index
+};
+struct WBatchDecArgs {
+    const uint8_t* comp;          // any alignment
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint32_t* lut;          // WideDecArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint8_t* letters;       // [nleaves * width], readable in whole dwords
+    uint32_t nleaves;
+    uint32_t width;
+    uint32_t cu_count;
+    const uint32_t* sub;          // required
+    const uint64_t* idx_off;
+    const uint64_t* off;          // the letter counts and output positions
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    uint8_t* out;                 // aligned to min(width, 16)
+    uint32_t* status;             // status_in passed through, kBatchOk or kBatchCorrupt
+};
+hipError_t launch_wbatch_bits(const WBatchEncArgs& a, hipStream_t s);   // k_wbatch_bits only (the scan: launch_batch_scan)
+hipError_t launch_wbatch_pack(const WBatchEncArgs& a, hipStream_t s);
+hipError_t launch_wbatch_decode(const WBatchDecArgs& a, hipStream_t s);
+// k_batch_scan alone (batch_codec.hip): comp_off and idx_off from bits and off
+hipError_t launch_batch_scan(const BatchBitsArgs& a, hipStream_t s);
+// diagnostics (huffgpu_wide.h huff_diag_wbatch_*): the three launchers' tables
+// of compiled builds as one enumeration, k_wbatch_bits (20), k_wbatch_pack (30),
+// k_wbatch_decode (9), with process-wide launch counts. name: null past the last row.
+uint32_t wbatch_builds();
+const char* wbatch_build_name(uint32_t i);
+uint64_t wbatch_build_launches(uint32_t i);
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

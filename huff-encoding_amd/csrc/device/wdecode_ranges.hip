@@ -31,6 +31,7 @@
 
 #include "../host/wrange_plan.hpp"
 #include "bitreader.hpp"
+#include "wide_tables.hpp"
 
 namespace huff::dev {
 
@@ -55,10 +56,6 @@ constexpr uint32_t kLdsMinBlocks = HUFF_WRANGE_LDS_MIN;
 constexpr uint64_t kMaxGrid = 0x7FFFFFFFull;
 constexpr size_t kLetterLdsMax = HUFF_WRANGE_LETTER_LDS_MAX;  // stage the leaf letters in LDS up to this
 
-struct U128 {
-    uint64_t lo, hi;
-};
-
 // BitReader over the wide table's entries (len in bits 24..30)
 struct WideBitReader : BitReader {
     __device__ __forceinline__ uint32_t peek(const BitSrc& src, const Lut& t) {
@@ -72,32 +69,6 @@ struct WideBitReader : BitReader {
         return e;
     }
 };
-
-// letter j of a 16-byte group of letters
-template <typename T>
-__device__ __forceinline__ void put_letter(uint32_t (&w)[4], uint32_t j, T v) {
-    if constexpr (sizeof(T) >= 4) {
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(&v);
-#pragma unroll
-        for (uint32_t k = 0; k < sizeof(T) / 4; ++k) w[j * (sizeof(T) / 4) + k] = p[k];
-    } else {
-        constexpr uint32_t per = 4 / sizeof(T);
-        w[j / per] |= static_cast<uint32_t>(v) << (8 * sizeof(T) * (j % per));
-    }
-}
-template <typename T>
-__device__ __forceinline__ T get_letter(const uint32_t (&w)[4], uint32_t j) {
-    if constexpr (sizeof(T) >= 4) {
-        T v;
-        uint32_t* p = reinterpret_cast<uint32_t*>(&v);
-#pragma unroll
-        for (uint32_t k = 0; k < sizeof(T) / 4; ++k) p[k] = w[j * (sizeof(T) / 4) + k];
-        return v;
-    } else {
-        constexpr uint32_t per = 4 / sizeof(T);
-        return static_cast<T>(w[j / per] >> (8 * sizeof(T) * (j % per)));
-    }
-}
 
 // the first bit of block j, which the index has an entry for
 __device__ __forceinline__ uint64_t block_start(const WRangesArgs& a, uint64_t j) {

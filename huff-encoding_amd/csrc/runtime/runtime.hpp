@@ -133,6 +133,7 @@ struct TaggedWords {
 namespace huff {
 struct IndexlessStep;
 struct FileWs;
+struct WBatchWs;
 }
 
 struct huff_wenc;
@@ -173,6 +174,8 @@ struct huff_ctx {
     // the task decoder of index-free wide-letter decodes (wide_rt.cpp), kept
     // so repeated decodes reuse its buffers and uploaded tables
     std::shared_ptr<huff_wenc> wdec_ws;
+    // the uploaded tables of the wide batch calls (wbatch_rt.cpp), likewise
+    std::shared_ptr<huff::WBatchWs> wbatch_ws;
     uint64_t lut_tree_id = 0;
 
     // kernel timing

@@ -297,19 +297,32 @@ namespace huff {
 
 Status wweights_map_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, size_t n,
                          std::vector<uint8_t>& uniq, std::vector<uint64_t>& counts) {
+    // the letters staged, then the device routine
+    uniq.clear();
+    counts.clear();
+    if (!valid_width(width)) return Status::err(HUFF_E_INVALID_ARG, "letter width must be 1, 2, 4, 8 or 16 bytes");
+    if (n == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    const size_t nb = n * width;
+    HUFF_TRY(ctx->d_in.ensure(nb + 16));
+    HIP_TRY(hipMemcpyAsync(ctx->d_in.p, letters, nb, hipMemcpyHostToDevice, ctx->stream));
+    return wweights_map_dev(ctx, width, static_cast<const uint8_t*>(ctx->d_in.p), n, uniq, counts);
+}
+
+Status wweights_map_dev(huff_ctx* ctx, uint32_t width, const uint8_t* d_letters, size_t n,
+                        std::vector<uint8_t>& uniq, std::vector<uint64_t>& counts) {
     // build_weights_map (weights.rs:82-123) on the device (wweights.hip),
     // distinct letters in ascending order
     uniq.clear();
     counts.clear();
     if (!valid_width(width)) return Status::err(HUFF_E_INVALID_ARG, "letter width must be 1, 2, 4, 8 or 16 bytes");
     if (n == 0) return Status::ok();
+    if (reinterpret_cast<uintptr_t>(d_letters) & (width - 1))  // width <= 16
+        return Status::err(HUFF_E_INVALID_ARG, "letters must be aligned to the letter width");
     HUFF_TRY(ctx->activate());
     hipStream_t s = ctx->stream;
-    const size_t nb = n * width;
-    HUFF_TRY(ctx->d_in.ensure(nb + 16));
-    HIP_TRY(hipMemcpyAsync(ctx->d_in.p, letters, nb, hipMemcpyHostToDevice, s));
     dev::WCountArgs a{};
-    a.in = static_cast<const uint8_t*>(ctx->d_in.p);
+    a.in = d_letters;
     a.n = n;
     a.width = width;
     const auto put = [&](uint64_t lo, uint64_t hi, uint64_t c) {

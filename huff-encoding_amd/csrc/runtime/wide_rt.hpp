@@ -73,8 +73,29 @@ struct huff_wenc {
 };
 
 namespace huff {
+// the device tables of the last trees a context's wide batch calls used
+// (wbatch_rt.cpp), kept so that calls under one tree upload them once
+struct WBatchWs {
+    DevBuf table, lut, letters;
+    uint64_t enc_tree = 0, dec_tree = 0;
+};
+// build_weights_map of n letters in HBM (d_letters aligned to min(width, 16)):
+// the distinct letters in ascending order and their counts
+Status wweights_map_dev(huff_ctx* ctx, uint32_t width, const uint8_t* d_letters, size_t n, std::vector<uint8_t>& uniq,
+                        std::vector<uint64_t>& counts);
+// the same of host letters: staged into ctx->d_in, then wweights_map_dev
 Status wweights_map_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, size_t n,
                          std::vector<uint8_t>& uniq, std::vector<uint64_t>& counts);
+// huff_wbatch_bits / _pack / _decode (wbatch_rt.cpp; device/wbatch.hip): every
+// pointer but ctx and t is a device pointer, the calls are synchronous
+Status wbatch_bits(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_in, const uint64_t* d_off, uint32_t nstreams,
+                   uint64_t* d_bits, uint64_t* d_comp_off, uint64_t* d_idx_off, uint64_t* d_missing, uint32_t* d_status);
+Status wbatch_pack(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_in, const uint64_t* d_off, const uint64_t* d_bits,
+                   const uint64_t* d_comp_off, const uint64_t* d_idx_off, uint32_t* d_status, uint32_t nstreams,
+                   uint8_t* d_out, size_t out_cap, uint32_t* d_sub, size_t sub_cap);
+Status wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                     const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_idx_off, const uint64_t* d_off,
+                     const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out, uint32_t* d_status);
 Status wcompress_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, size_t n, const huff_wtree* t,
                       huff_wcompress_data** out, u128* missing);
 Status wdecompress_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint8_t* out, size_t cap_letters,

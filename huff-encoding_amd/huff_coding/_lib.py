@@ -202,6 +202,13 @@ SIGNATURES = [
     ("huff_wcd_attach_index", i, [vp, vp, vp, sz, u64p]),
     ("huff_wenc_from_indexed_stream", i, [vp, vp, vp, sz, C.c_uint8, vp, sz, C.POINTER(vp), u64p]),
     ("huff_diag_wrange_staged_bytes", C.c_uint64, []),
+    ("huff_dev_wweights_map", i, [vp, C.c_uint32, vp, sz, vp, vp, sz, szp]),
+    ("huff_wbatch_bits", i, [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+    ("huff_wbatch_pack", i, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, sz]),
+    ("huff_wbatch_decode", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]),
+    ("huff_diag_wbatch_builds", C.c_uint32, []),
+    ("huff_diag_wbatch_build_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_wbatch_build_launches", C.c_uint64, [C.c_uint32]),
 ]
 
 _lib = None
@@ -276,6 +283,14 @@ def wrange_build_launches() -> dict:
     L = load()
     return {L.huff_diag_wrange_build_name(k).decode(): L.huff_diag_wrange_build_launches(k)
             for k in range(L.huff_diag_wrange_builds())}
+
+
+def wbatch_build_launches() -> dict:
+    """{build name: launches so far} of the wide batch kernels' compiled builds
+    (huff_diag_wbatch_build_*): k_wbatch_bits, k_wbatch_pack, k_wbatch_decode rows, in that order"""
+    L = load()
+    return {L.huff_diag_wbatch_build_name(k).decode(): L.huff_diag_wbatch_build_launches(k)
+            for k in range(L.huff_diag_wbatch_builds())}
 
 
 def last_error() -> str:

@@ -1,0 +1,226 @@
+"""Many small streams of wide letters under one shared tree (include/huffgpu_wide.h
+huff_wbatch_*, huff_dev_wweights_map): compress_with_tree (comp.rs:419-451) and
+decompress (comp.rs:487-519) of a whole batch in one launch each, with a
+restart index per stream, as huff_coding.batch does for byte streams.
+
+Device tensors in, device tensors out. Letters are a torch tensor of uint8,
+int16, int32 or int64 (a signed type and its unsigned twin share the code: the
+letters are their bit patterns), or a uint8 tensor with dtype=wide.U128 /
+wide.I128 for 16-byte letters (16 bytes per letter, little-endian); offsets
+are int64, in letters:
+
+    w = weights_map_dev(ctx, letters)                      # {letter: count}, as wide.build_weights_map
+    tree = wide.WideTree.from_weights(w, np.uint16)        # the tree every stream shares
+    c = compress_batch(ctx, letters, offsets, tree)        # WideBatchCompressed
+    c.comp[c.comp_offsets[s]: c.comp_offsets[s + 1]]       # stream s; padding (8 - c.bits[s] % 8) % 8
+    c.sub[c.index_offsets[s] + j]                          # bit offset of its letter 64 j
+    letters2, status = decompress_batch(ctx, c)
+
+or call by call:
+
+    bits, comp_off, idx_off, missing, status = wbatch_bits(ctx, tree, letters, offsets)
+    wbatch_pack(ctx, tree, letters, offsets, bits, comp_off, idx_off, status, out, sub)
+    status2 = wbatch_decode(ctx, tree, out, comp_off, bits, sub, idx_off, offsets, status, letters_out)
+
+A stream that cannot be coded gets a status (E_EMPTY_COMP for no letters,
+E_MISSING_LETTER with missing[s] = the index of the first letter without a
+code, E_INVALID_ARG for 2^32 bits or more) and owns no bytes; a stream that
+does not decode along its index gets E_CORRUPT, the others are unaffected.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import load
+from .batch import _dev, _p
+from .wide import I128, U128, LetterType, WideTree
+
+E_INVALID_ARG = _lib.E_INVALID_ARG
+E_MISSING_LETTER = _lib.E_MISSING_LETTER
+E_BUFFER_TOO_SMALL = _lib.E_BUFFER_TOO_SMALL
+E_CORRUPT = _lib.E_CORRUPT
+E_EMPTY_COMP = _lib.E_EMPTY_COMP
+E_CODE_TOO_LONG = _lib.E_CODE_TOO_LONG
+
+IDX = 64  # letters per restart index entry
+
+_TORCH_WIDTH = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
+_NP_OF = {torch.uint8: np.uint8, torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32,
+          torch.int64: np.int64}
+
+
+def _check(rc: int):
+    from . import _check as chk
+
+    chk(rc)
+
+
+def letter_width(letters: torch.Tensor, dtype=None) -> int:
+    """bytes per letter of a letters tensor (dtype: wide.U128 / wide.I128 for a uint8 tensor of 16-byte letters)"""
+    if dtype in (U128, I128):
+        if letters.dtype != torch.uint8 or letters.numel() % 16:
+            raise TypeError("16-byte letters travel as a uint8 tensor of 16 bytes per letter")
+        return 16
+    if dtype is not None:
+        w = LetterType(dtype).width
+        if _TORCH_WIDTH.get(letters.dtype) != w:
+            raise TypeError(f"{letters.dtype} does not hold letters of {w} bytes")
+        return w
+    if letters.dtype not in _TORCH_WIDTH:
+        raise TypeError(f"{letters.dtype} is not a letter type (uint8, int16, int32, int64)")
+    return _TORCH_WIDTH[letters.dtype]
+
+
+def _letters(letters: torch.Tensor, width: int) -> int:
+    """the letter count of a contiguous device tensor of `width`-byte letters"""
+    assert letters.is_cuda and letters.is_contiguous()
+    return letters.numel() * letters.element_size() // width
+
+
+def weights_map_dev(ctx, letters: torch.Tensor, dtype=None) -> dict:
+    """build_weights_map (weights.rs:82-123) of letters already on the device
+    (huff_dev_wweights_map): {letter: count} in ascending order of the letters'
+    bit patterns, as wide.build_weights_map returns for the same letters on the host"""
+    width = letter_width(letters, dtype)
+    lt = LetterType(dtype if dtype is not None else _NP_OF[letters.dtype])
+    n = _letters(letters, width)
+    cnt = C.c_size_t()
+    cap = max(1, min(n, 1 << 16))
+    while True:
+        u = np.zeros(cap, lt.np)
+        w = np.zeros(cap, np.uint64)
+        rc = load().huff_dev_wweights_map(ctx.h, width, _p(letters) if n else None, n, u.ctypes.data,
+                                          w.ctypes.data, cap, C.byref(cnt))
+        if rc == E_BUFFER_TOO_SMALL and cnt.value > cap:
+            cap = cnt.value
+            continue
+        _check(rc)
+        break
+    return dict(zip(lt.values(u[: cnt.value]), (int(x) for x in w[: cnt.value])))
+
+
+def _offsets_inside(offsets: torch.Tensor, n: int, what: str):
+    """every offset in [0, n]: one device reduction, one host read"""
+    if offsets.numel():
+        ok = (offsets.min() >= 0) & (offsets.max() <= n)
+        if not bool(ok.item()):
+            raise ValueError(f"{what} must lie inside their buffer")
+
+
+def wbatch_bits(ctx, tree: WideTree, letters: torch.Tensor, offsets: torch.Tensor):
+    """(bits [S], comp_offsets [S + 1], index_offsets [S + 1], missing [S], status [S]) of
+    huff_wbatch_bits; missing holds u64 indices as int64 (-1: none)"""
+    width = tree.ltype.width
+    ns = offsets.numel() - 1
+    assert ns >= 0
+    _dev(offsets, torch.int64)
+    _offsets_inside(offsets, _letters(letters, width), "offsets")
+    dev = offsets.device
+    bits = torch.zeros(ns, dtype=torch.int64, device=dev)
+    comp_offsets = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
+    index_offsets = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
+    missing = torch.full((ns,), -1, dtype=torch.int64, device=dev)
+    status = torch.zeros(ns, dtype=torch.int32, device=dev)
+    _check(load().huff_wbatch_bits(ctx.h, tree.h, _p(letters), _p(offsets), ns, _p(bits), _p(comp_offsets),
+                                   _p(index_offsets), _p(missing), _p(status)))
+    return bits, comp_offsets, index_offsets, missing, status
+
+
+def wbatch_pack(ctx, tree: WideTree, letters: torch.Tensor, offsets: torch.Tensor, bits: torch.Tensor,
+                comp_offsets: torch.Tensor, index_offsets: torch.Tensor, status: torch.Tensor, out: torch.Tensor,
+                sub: torch.Tensor | None) -> None:
+    """huff_wbatch_pack into out (u8, its numel is the capacity) and sub (int32
+    holding u32 offsets, or None: no index); raises HuffError
+    (E_BUFFER_TOO_SMALL) with nothing written if either is short. status is
+    updated in place where a stream's letters do not add up to bits[s]."""
+    width = tree.ltype.width
+    ns = offsets.numel() - 1
+    assert ns >= 0
+    _dev(offsets, torch.int64)
+    _offsets_inside(offsets, _letters(letters, width), "offsets")
+    _dev(bits, torch.int64, (ns,))
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(index_offsets, torch.int64, (ns + 1,))
+    _dev(status, torch.int32, (ns,))
+    _dev(out, torch.uint8)
+    if sub is not None:
+        _dev(sub, torch.int32)
+    _check(load().huff_wbatch_pack(ctx.h, tree.h, _p(letters), _p(offsets), _p(bits), _p(comp_offsets),
+                                   _p(index_offsets), _p(status), ns, _p(out), out.numel(), _p(sub),
+                                   sub.numel() if sub is not None else 0))
+
+
+def wbatch_decode(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor,
+                  sub: torch.Tensor, index_offsets: torch.Tensor, offsets: torch.Tensor, status_in: torch.Tensor,
+                  out: torch.Tensor) -> torch.Tensor:
+    """huff_wbatch_decode: the letters of stream s to out[offsets[s]:offsets[s + 1]]
+    (in letters); sub None raises HuffError (E_INVALID_ARG). Returns the per-stream status [S] (int32)."""
+    width = tree.ltype.width
+    ns = offsets.numel() - 1
+    assert ns >= 0
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(offsets, torch.int64)
+    _dev(status_in, torch.int32, (ns,))
+    _dev(index_offsets, torch.int64, (ns + 1,))
+    if sub is not None:
+        _dev(sub, torch.int32)
+    # no stream reads outside comp or sub or writes outside out: one host read
+    if ns > 0 and sub is not None:
+        ok = (offsets.min() >= 0) & (offsets.max() <= _letters(out, width))
+        ok &= (comp_offsets.min() >= 0) & (comp_offsets.max() <= comp.numel())
+        ok &= (index_offsets.min() >= 0) & (index_offsets.max() <= sub.numel())
+        if not bool(ok.item()):
+            raise ValueError("offsets must lie inside their buffers")
+    status = torch.zeros(ns, dtype=torch.int32, device=offsets.device)
+    _check(load().huff_wbatch_decode(ctx.h, tree.h, _p(comp), _p(comp_offsets), _p(bits), _p(sub), _p(index_offsets),
+                                     _p(offsets), _p(status_in), ns, _p(out), _p(status)))
+    return status
+
+
+@dataclass
+class WideBatchCompressed:
+    comp: torch.Tensor           # u8: the streams, tightly concatenated
+    comp_offsets: torch.Tensor   # [S + 1] int64, in bytes
+    bits: torch.Tensor           # [S] int64
+    sub: torch.Tensor            # int32 (u32 entries): the restart index
+    index_offsets: torch.Tensor  # [S + 1] int64, in entries
+    status: torch.Tensor         # [S] int32
+    missing: torch.Tensor        # [S] int64: the first letter without a code (E_MISSING_LETTER), else -1
+    offsets: torch.Tensor        # [S + 1] int64, in letters
+    tree: WideTree
+    width: int
+    letters_dtype: torch.dtype = torch.uint8  # the tensor type decompress_batch returns letters in
+
+
+def compress_batch(ctx, letters: torch.Tensor, offsets: torch.Tensor, tree: WideTree) -> WideBatchCompressed:
+    """compress_with_tree of every stream letters[offsets[s]:offsets[s + 1]] under
+    `tree`: huff_wbatch_bits, one host read of the two totals, huff_wbatch_pack"""
+    width = tree.ltype.width
+    if letters.element_size() not in (1, width):
+        raise TypeError(f"{letters.dtype} does not hold letters of {width} bytes")
+    bits, comp_offsets, index_offsets, missing, status = wbatch_bits(ctx, tree, letters, offsets)
+    totals = torch.stack((comp_offsets[-1], index_offsets[-1])).tolist()
+    comp = torch.empty(totals[0], dtype=torch.uint8, device=letters.device)
+    sub = torch.empty(totals[1], dtype=torch.int32, device=letters.device)
+    wbatch_pack(ctx, tree, letters, offsets, bits, comp_offsets, index_offsets, status, comp, sub)
+    return WideBatchCompressed(comp, comp_offsets, bits, sub, index_offsets, status, missing, offsets, tree, width,
+                               letters.dtype)
+
+
+def decompress_batch(ctx, c: WideBatchCompressed):
+    """(letters, status): every stream's letters at its offsets, in a tensor of
+    the type compress_batch was given (zero where a stream has a status), and
+    the per-stream status of huff_wbatch_decode"""
+    n = int(c.offsets.max().item()) if c.offsets.numel() else 0
+    per = c.width // torch.empty(0, dtype=c.letters_dtype).element_size()
+    out = torch.zeros(n * per, dtype=c.letters_dtype, device=c.comp.device)
+    status = wbatch_decode(ctx, c.tree, c.comp, c.comp_offsets, c.bits, c.sub, c.index_offsets, c.offsets, c.status,
+                           out)
+    return out, status

@@ -263,7 +263,113 @@ int huff_wdecompress_range(huff_ctx* ctx, const huff_wcompress_data* cd, uint64_
 int huff_dev_wdecompress(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
                          uint8_t padding, void* d_out, size_t out_cap_letters, size_t* n_out);
 
+/* ---------------- many small streams under one tree ---------------------- */
+/* build_weights_map of n letters already in HBM: huff_wweights_map without the
+ * copy from the host (one routine counts for both). d_letters is aligned to
+ * min(width, 16) bytes (else HUFF_E_INVALID_ARG); letters_out, weights_out and
+ * count are host pointers; same outputs, same ascending order, *count set even
+ * when cap is short. A tree for huff_wbatch_* is huff_wtree_from_weights of
+ * these. */
+int huff_dev_wweights_map(huff_ctx* ctx, uint32_t width, const void* d_letters, size_t n, void* letters_out,
+                          uint64_t* weights_out, size_t cap, size_t* count);
+/* compress_with_tree (comp.rs:419-451) and decompress (comp.rs:487-519) of a
+ * batch of many small streams of wide letters under ONE caller-given tree, with
+ * a restart index per stream: huff_batch_bits / _pack / _decode (huffgpu.h) for
+ * letters of the tree's width. All arrays are device pointers; the calls are
+ * synchronous on the context's stream.
+ *
+ * Batch layout: stream s is the letters [d_offsets[s], d_offsets[s + 1]) of
+ * d_in, offsets in letters; d_in is 16-byte aligned (as for huff_wenc_create),
+ * a stream may start at any letter; a descending pair is an empty stream.
+ * Output layout: every stream is the reference's compress_with_tree stream for
+ * it alone: ceil(d_bits[s] / 8) bytes at d_out + d_comp_offsets[s], the first
+ * code at the first byte's MSB, (8 - bits % 8) % 8 zero pad bits, the streams
+ * tightly one after another; d_sub[d_index_offsets[s] + j] (u32) is the bit
+ * offset, from the stream's first bit, of its letter 64 j (ceil(n_s / 64)
+ * entries).
+ *
+ *  huff_wbatch_bits:   d_bits[s] = the sum of the code lengths of the stream's
+ *                      letters; d_comp_offsets and d_index_offsets the
+ *                      exclusive scans (nstreams + 1 entries each, scanned on
+ *                      the device) of ceil(bits / 8) and of ceil(n_s / 64) (the
+ *                      latter for every stream, coded or not). d_status[s]:
+ *                      HUFF_OK; HUFF_E_EMPTY_COMP for a stream of no letters
+ *                      (comp.rs:443-449, as huff_wcompress_with_tree answers);
+ *                      HUFF_E_MISSING_LETTER when a letter has no code, with
+ *                      d_missing[s] (u64) the index within the stream of the
+ *                      first such letter in input order (all ones otherwise);
+ *                      HUFF_E_INVALID_ARG for 2^32 bits or more (the entries
+ *                      are 32-bit). A stream that is not HUFF_OK has 0 bits and
+ *                      owns 0 bytes. Before any device work:
+ *                      HUFF_E_INVALID_ARG for a null pointer or a d_in that is
+ *                      not 16-byte aligned, HUFF_E_CODE_TOO_LONG for a tree with
+ *                      a code longer than 56 bits. nstreams = 0: HUFF_OK, no
+ *                      launch.
+ *  huff_wbatch_pack:   reads the two totals back first and returns
+ *                      HUFF_E_BUFFER_TOO_SMALL with nothing written if out_cap
+ *                      (bytes) or sub_cap (entries) is short; d_sub NULL: no
+ *                      index. A stream that is not HUFF_OK writes nothing.
+ *                      Every byte of d_out has exactly one writer and no
+ *                      zero-filled output is assumed; nothing outside a
+ *                      stream's own bytes and entries is written. d_status[s]
+ *                      becomes HUFF_E_INVALID_ARG where the letters do not add
+ *                      up to d_bits[s] (the arrays were not huff_wbatch_bits'
+ *                      for this input and tree).
+ *  huff_wbatch_decode: n_s letters of stream s to d_out + d_offsets[s] * width
+ *                      (d_out aligned to min(width, 16)). d_sub is required
+ *                      (NULL: HUFF_E_INVALID_ARG). huff_batch_decode's rule:
+ *                      block j starts at its entry and must end exactly at the
+ *                      next (the last block at d_bits[s]), entry 0 must be 0,
+ *                      the stream's bytes must be ceil(bits / 8) and its
+ *                      entries ceil(n_s / 64). d_status[s] = d_status_in[s] if
+ *                      that is not HUFF_OK (nothing written), else HUFF_OK or
+ *                      HUFF_E_CORRUPT. A corrupt stream, whatever its entries
+ *                      or d_bits say, reads only its own compressed bytes and
+ *                      entries, writes only its own n_s letters and leaves the
+ *                      other streams alone. HUFF_E_CODE_TOO_LONG as above.
+ *
+ * The tree's tables are those of the single-stream calls (the encoder's hash
+ * table, the long-code decoder's table and leaf letters); a context keeps them
+ * on the device from call to call while the tree stays the same. One wave takes
+ * a stream; a workgroup of 16 waves loads the tables once and loops over
+ * streams ("Many small wide streams"), so the calls pay for the
+ * tables per workgroup, not per stream.
+ * Cost, measured on an MI355X on 10,000 streams x 8,192 letters
+ * (tools/wbatchbench.py, DESIGN.md §9, "Many small wide streams"; medians of 10,
+ * one process): for 2- / 4-byte letters, Zipf(1.2) over 4,096 letters, the
+ * bits kernel takes 0.059 / 0.085 ms, the pack 0.089 / 0.118 ms and the decode
+ * 0.60 / 0.78 ms; uniform over 65,536 / 2^20 letters (tables read from L2)
+ * 0.37 / 1.12, 0.39 / 1.16 and 2.97 / 6.85 ms. bits + pack with their
+ * allocations (compress_batch) take 0.44-2.6 ms of wall time and the decode
+ * 0.79-7.1 ms, against 0.9-4.9 s and 0.7-98 s for one huff_wenc job per stream
+ * (extrapolated from 200 streams): 1,460-2,160 and 470-13,900 times faster.
+ * Against the same letters as ONE stream the bits and pack kernels take 0.64-
+ * 0.95 of huff_wenc_bits / _pack's kernel time, but THE DECODE TAKES 6-10
+ * TIMES huff_wenc_decode's: where one large stream will do, that is the faster
+ * decoder. huff_dev_wweights_map took 3.5-8.1 ms there, 682 ms for 2^20
+ * distinct letters. */
+int huff_wbatch_bits(huff_ctx* ctx, const huff_wtree* t, const void* d_in, const uint64_t* d_offsets, uint32_t nstreams,
+                     uint64_t* d_bits, uint64_t* d_comp_offsets, uint64_t* d_index_offsets, uint64_t* d_missing,
+                     uint32_t* d_status);
+int huff_wbatch_pack(huff_ctx* ctx, const huff_wtree* t, const void* d_in, const uint64_t* d_offsets,
+                     const uint64_t* d_bits, const uint64_t* d_comp_offsets, const uint64_t* d_index_offsets,
+                     uint32_t* d_status, uint32_t nstreams, uint8_t* d_out, size_t out_cap, uint32_t* d_sub,
+                     size_t sub_cap);
+int huff_wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                       const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_index_offsets,
+                       const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, void* d_out,
+                       uint32_t* d_status);
+
 /* ---------------- diagnostics (not reference functions) ------------------ */
+/* huff_wbatch_* take their kernels from tables of their own: 20 k_wbatch_bits
+ * rows (letter width x u64 or u32 table values x table in LDS or read in
+ * place), 30 k_wbatch_pack rows (the same with the three entry formats: codes
+ * <= 56 bits, <= 16 in pairs, <= 27) and 9 k_wbatch_decode rows (letter type x
+ * leaf letters in LDS or in global memory, without <uint8_t, false>),
+ * enumerated in that order; names and counts as huff_diag_wide_*. */
+uint32_t huff_diag_wbatch_builds(void);
+const char* huff_diag_wbatch_build_name(uint32_t i);
+uint64_t huff_diag_wbatch_build_launches(uint32_t i);
 /* The wide launchers take their kernels from tables of compiled builds: 20
  * k_wbits (pass 1), 32 k_wpack (pass 2), 30 k_wdec_task (codes <= 32 bits)
  * and 10 k_wdecode (longer codes) rows, enumerated in that order.
