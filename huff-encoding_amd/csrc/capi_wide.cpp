@@ -454,9 +454,31 @@ int huff_wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp
     });
 }
 
+int huff_wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                              const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_index_offsets,
+                              const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams,
+                              const uint32_t* d_req_stream, const uint64_t* d_req_first, const uint64_t* d_req_count,
+                              const uint64_t* d_req_out_begin, uint32_t nreq, void* d_out, size_t out_cap_letters,
+                              uint32_t* d_req_status) {
+    if (!ctx || !t || (nreq && (!d_comp || !d_comp_offsets || !d_bits || !d_index_offsets || !d_offsets ||
+                                !d_status_in || !d_req_stream || !d_req_first || !d_req_count || !d_req_out_begin ||
+                                !d_out || !d_req_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (nreq && !d_sub) return fail(HUFF_E_INVALID_ARG, "a letter range of a wide batch needs its restart index (d_sub)");
+    return guarded([&] {
+        return huff::wbatch_decode_ranges(ctx, t, d_comp, d_comp_offsets, d_bits, d_sub, d_index_offsets, d_offsets,
+                                          d_status_in, nstreams, d_req_stream, d_req_first, d_req_count,
+                                          d_req_out_begin, nreq, static_cast<uint8_t*>(d_out), out_cap_letters,
+                                          d_req_status);
+    });
+}
+
 uint32_t huff_diag_wbatch_builds(void) { return huff::dev::wbatch_builds(); }
 const char* huff_diag_wbatch_build_name(uint32_t i) { return huff::dev::wbatch_build_name(i); }
 uint64_t huff_diag_wbatch_build_launches(uint32_t i) { return huff::dev::wbatch_build_launches(i); }
+uint32_t huff_diag_wbatch_range_builds(void) { return huff::dev::wbatch_range_builds(); }
+const char* huff_diag_wbatch_range_build_name(uint32_t i) { return huff::dev::wbatch_range_build_name(i); }
+uint64_t huff_diag_wbatch_range_build_launches(uint32_t i) { return huff::dev::wbatch_range_build_launches(i); }
 
 // diagnostics: which wide-letter build ran, from which restart form
 uint32_t huff_diag_wide_builds(void) { return huff::dev::wide_builds(); }

@@ -726,6 +726,43 @@ hipError_t launch_batch_scan(const BatchBitsArgs& a, hipStream_t s);
 uint32_t wbatch_builds();
 const char* wbatch_build_name(uint32_t i);
 uint64_t wbatch_build_launches(uint32_t i);
+// Letter ranges of chosen streams of such a batch through the restart index
+// (wbatch_ranges.hip; host/wbatch_range_plan.hpp): request r is the letters
+// [req_first[r], req_first[r] + req_count[r]) of stream req_stream[r], stored
+// at out + out_begin[r] * width; only the kWBatchBlock-letter blocks it touches
+// are decoded. One wave per request, kWBatchWaves waves per persistent workgroup.
+struct WBatchRangesArgs {
+    const uint8_t* comp;          // any alignment
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint32_t* lut;          // WideDecArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint8_t* letters;       // [nleaves * width], readable in whole dwords
+    uint32_t nleaves;
+    uint32_t width;
+    uint32_t cu_count;
+    const uint32_t* sub;          // required
+    const uint64_t* idx_off;
+    const uint64_t* off;          // the letter counts
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    const uint32_t* req_stream;   // [nreq]
+    const uint64_t* req_first;    // in letters, as the next two
+    const uint64_t* req_count;
+    const uint64_t* out_begin;
+    uint32_t nreq;
+    uint8_t* out;                 // aligned to min(width, 16)
+    uint64_t out_cap;             // letters
+    uint32_t* status;             // [nreq]: kBatchInvalid (no such stream, range or slot), the stream's
+                                  // status_in, kBatchOk or kBatchCorrupt
+};
+hipError_t launch_wbatch_decode_ranges(const WBatchRangesArgs& a, hipStream_t s);
+// diagnostics (huffgpu_wide.h huff_diag_wbatch_range_*): the launcher's table of
+// the 9 compiled k_wbatch_decode_ranges builds with process-wide launch counts.
+// name: null past the last row.
+uint32_t wbatch_range_builds();
+const char* wbatch_range_build_name(uint32_t i);
+uint64_t wbatch_range_build_launches(uint32_t i);
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

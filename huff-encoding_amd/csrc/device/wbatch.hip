@@ -44,6 +44,7 @@
 #include "../host/wbatch_plan.hpp"
 #include "batch_stream.hpp"
 #include "pack_emit.hpp"
+#include "wbatch_walk.hpp"
 #include "wide_tables.hpp"
 
 namespace huff::dev {
@@ -220,74 +221,7 @@ __global__ __launch_bounds__(kThreads) void k_wbatch_pack(WBatchEncArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// 64 bits of the stream from bit pos, left-aligned
-__device__ __forceinline__ uint64_t src_window(const BatchSrc& src, uint32_t pos) {
-    const uint32_t wi = pos >> 5, sh = pos & 31;
-    const uint64_t hi = (static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1);
-    return sh ? (hi << sh) | (src.word(wi + 2) >> (32 - sh)) : hi;
-}
-
-// cnt codes from bit `start`, which must end exactly at bit `end` (start <=
-// end); the letters go to out[0, cnt). False: a window without a code, a code
-// crossing `end`, or an end other than `end`. The table is WideDecTables::lut
-// as k_wdecode_ranges reads it: a leaf entry len << 24 | leaf index, codes
-// longer than the window's valid bits or the primary index looked up afresh.
-template <typename T>
-__device__ __forceinline__ bool decode_block(const BatchSrc& src, const uint32_t* __restrict__ prim,
-                                             const uint32_t* __restrict__ glob, uint32_t K,
-                                             const T* __restrict__ letters, uint32_t start, uint32_t end, uint32_t cnt,
-                                             T* __restrict__ out) {
-    constexpr uint32_t L = wbatch_group(sizeof(T));
-    uint32_t pos = start, wi = start >> 5;
-    uint64_t buf = ((static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1)) << (start & 31);
-    uint32_t nb = 64 - (start & 31);
-    wi += 2;
-    for (uint32_t done = 0; done < cnt; done += L) {
-        const uint32_t m = cnt - done < L ? cnt - done : L;
-        uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (uint32_t k = 0; k < L; ++k) {
-            if (k < m) {
-                if (nb <= 32) {
-                    buf |= static_cast<uint64_t>(src.word(wi)) << (32 - nb);
-                    ++wi;
-                    nb += 32;
-                }
-                uint32_t e = prim[buf >> (64 - K)];
-                if ((e & kLutPtr) || ((e >> 24) & 0x7Fu) > nb) {
-                    const uint64_t win = src_window(src, pos);
-                    e = prim[win >> (64 - K)];
-                    for (uint32_t d = K; (e & kLutPtr) && d <= 56; d += 8)
-                        e = glob[(e & ~kLutPtr) + static_cast<uint32_t>((win >> (56 - d)) & 0xFFu)];
-                    if (e & kLutPtr) return false;
-                }
-                const uint32_t len = (e >> 24) & 0x7Fu;
-                if (len == 0 || len > end - pos) return false;
-                pos += len;
-                if (len < nb) {
-                    buf <<= len;
-                    nb -= len;
-                } else {  // the window is used up (long codes): start again at pos
-                    wi = pos >> 5;
-                    buf = ((static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1)) << (pos & 31);
-                    nb = 64 - (pos & 31);
-                    wi += 2;
-                }
-                put_letter<T>(w, k, letters[e & 0xFFFFFFu]);
-            }
-        }
-        if (m == L) {
-            const uint4 v = make_uint4(w[0], w[1], w[2], w[3]);
-            __builtin_memcpy(out + done, &v, 16);  // aligned to the letter only
-        } else {
-#pragma unroll
-            for (uint32_t k = 0; k < L; ++k)
-                if (k < m) out[done + k] = get_letter<T>(w, k);
-        }
-    }
-    return pos == end;
-}
-
+// the walk of a block: wbatch_walk.hpp's decode_block
 template <typename T, bool LLDS>
 __global__ __launch_bounds__(kThreads) void k_wbatch_decode(WBatchDecArgs a) {
     // [1 << lut_bits primary entries][LLDS: the leaf letters, from a 16-byte boundary]
@@ -335,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void k_wbatch_decode(WBatchDecArgs a) {
             const uint32_t end = j + 1 < nblk ? sub[j + 1] : end_all;
             const uint32_t cnt = wbatch_block_letters(n, j);
             ok = ok && wbatch_block_sane(j, start, end, end_all) &&
-                 decode_block<T>(src, plut, a.lut, K, letters, start, end, cnt, out + j * kWBatchBlock);
+                 decode_block<T, false>(src, plut, a.lut, K, letters, start, end, cnt, 0, cnt, out + j * kWBatchBlock);
         }
         const bool bad = __ballot(!ok) != 0;
         if (lane == 0) a.status[s] = bad ? kBatchCorrupt : kBatchOk;
@@ -387,15 +321,6 @@ std::atomic<uint64_t> g_bits_launches[kNumBits], g_pack_launches[kNumPack], g_de
 
 // 0 .. 4 for letters of 1, 2, 4, 8, 16 bytes
 constexpr uint32_t width_index(uint32_t w) { return w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : w == 8 ? 3u : 4u; }
-
-// persistent grid: 1024-thread workgroups, at most 2 per CU (32 waves), one
-// where the LDS does not fit twice; never more than have a stream
-uint32_t persistent_grid(uint32_t nstreams, uint32_t cus, size_t lds) {
-    const uint32_t per_cu = lds * 2 + 2048 <= 160 * 1024 ? 2u : 1u;
-    const uint32_t g = (cus ? cus : 256) * per_cu;
-    const uint32_t need = wbatch_groups(nstreams);
-    return need < g ? need : g;
-}
 
 template <uint32_t N>
 hipError_t enc_go(const Build<EncKernel> (&builds)[N], std::atomic<uint64_t> (&launches)[N], uint32_t row,

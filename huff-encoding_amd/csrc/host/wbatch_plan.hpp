@@ -12,6 +12,7 @@
 // lanes x one block of kWBatchBlock letters.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 namespace huff {
@@ -26,6 +27,14 @@ constexpr uint64_t wbatch_stream(uint32_t wg, uint32_t wave, uint64_t it, uint32
 }
 // workgroups that have a stream at all
 constexpr uint32_t wbatch_groups(uint32_t nstreams) { return (nstreams + kWBatchWaves - 1) / kWBatchWaves; }
+// persistent grid: 1024-thread workgroups, at most 2 per CU (32 waves), one
+// where the LDS does not fit twice; never more than have a stream
+constexpr uint32_t persistent_grid(uint32_t nstreams, uint32_t cus, size_t lds) {
+    const uint32_t per_cu = lds * 2 + 2048 <= 160 * 1024 ? 2u : 1u;
+    const uint32_t g = (cus ? cus : 256) * per_cu;
+    const uint32_t need = wbatch_groups(nstreams);
+    return need < g ? need : g;
+}
 
 // letters of the stream [lo, hi) of the batch (a descending pair: empty)
 constexpr uint64_t wbatch_letters(uint64_t lo, uint64_t hi) { return hi > lo ? hi - lo : 0; }

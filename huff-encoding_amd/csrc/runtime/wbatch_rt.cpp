@@ -43,6 +43,43 @@ Status enc_table(huff_ctx* ctx, const huff_wtree* t, bool pack_pass, dev::WideAr
     return Status::ok();
 }
 
+// what the two decode calls refuse before any device work: an output off the
+// letter's alignment, a tree no wide batch was ever packed with
+Status dec_check(const huff_wtree* t, const uint8_t* d_out) {
+    const uint32_t W = t->t.width();
+    if (reinterpret_cast<uintptr_t>(d_out) & (W - 1))  // W <= 16
+        return Status::err(HUFF_E_INVALID_ARG, "output must be aligned to the letter width");
+    const WideDecTables* dt = nullptr;
+    HUFF_TRY(t->dec_tables(&dt));
+    if (dt->maxdepth > kWideMaxEncodeLen) return Status::err(HUFF_E_CODE_TOO_LONG, "code longer than 56 bits");
+    return Status::ok();
+}
+
+// the table fields of a decode: the tree's long-code table and leaf letters in
+// the context's buffers (the context is active); Args: WBatchDecArgs or WBatchRangesArgs
+template <class Args>
+Status dec_table(huff_ctx* ctx, const huff_wtree* t, Args& a) {
+    const WideDecTables* dt = nullptr;
+    HUFF_TRY(t->dec_tables(&dt));
+    hipStream_t s = ctx->stream;
+    WBatchWs& ws = workspace(ctx);
+    if (ws.dec_tree != t->id) {
+        HUFF_TRY(ws.lut.ensure(dt->lut.size() * 4));
+        HUFF_TRY(ws.letters.ensure((dt->letters.size() + 31) / 16 * 16));  // staged in whole dwords
+        HIP_TRY(hipMemcpyAsync(ws.lut.p, dt->lut.data(), dt->lut.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ws.letters.p, dt->letters.data(), dt->letters.size(), hipMemcpyHostToDevice, s));
+        HUFF_TRY(ctx->sync());
+        ws.dec_tree = t->id;
+    }
+    a.width = t->t.width();
+    a.lut = static_cast<const uint32_t*>(ws.lut.p);
+    a.lut_bits = dt->bits;
+    a.letters = static_cast<const uint8_t*>(ws.letters.p);
+    a.nleaves = static_cast<uint32_t>(dt->letters.size() / a.width);
+    a.cu_count = wide_cu_count(static_cast<uint32_t>(ctx->cu_count));
+    return Status::ok();
+}
+
 }  // namespace
 
 Status wbatch_bits(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_in, const uint64_t* d_off, uint32_t nstreams,
@@ -107,35 +144,15 @@ Status wbatch_pack(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_in, cons
 Status wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
                      const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_idx_off, const uint64_t* d_off,
                      const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out, uint32_t* d_status) {
-    const uint32_t W = t->t.width();
-    if (reinterpret_cast<uintptr_t>(d_out) & (W - 1))  // W <= 16
-        return Status::err(HUFF_E_INVALID_ARG, "output must be aligned to the letter width");
-    const WideDecTables* dt = nullptr;
-    HUFF_TRY(t->dec_tables(&dt));
-    if (dt->maxdepth > kWideMaxEncodeLen)  // no wide batch was ever packed with such a tree
-        return Status::err(HUFF_E_CODE_TOO_LONG, "code longer than 56 bits");
+    dev::WBatchDecArgs a{};
+    HUFF_TRY(dec_check(t, d_out));
     if (nstreams == 0) return Status::ok();
     HUFF_TRY(ctx->activate());
     hipStream_t s = ctx->stream;
-    WBatchWs& ws = workspace(ctx);
-    if (ws.dec_tree != t->id) {
-        HUFF_TRY(ws.lut.ensure(dt->lut.size() * 4));
-        HUFF_TRY(ws.letters.ensure((dt->letters.size() + 31) / 16 * 16));  // staged in whole dwords
-        HIP_TRY(hipMemcpyAsync(ws.lut.p, dt->lut.data(), dt->lut.size() * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(ws.letters.p, dt->letters.data(), dt->letters.size(), hipMemcpyHostToDevice, s));
-        HUFF_TRY(ctx->sync());
-        ws.dec_tree = t->id;
-    }
-    dev::WBatchDecArgs a{};
+    HUFF_TRY(dec_table(ctx, t, a));
     a.comp = d_comp;
     a.comp_off = d_comp_off;
     a.bits = d_bits;
-    a.lut = static_cast<const uint32_t*>(ws.lut.p);
-    a.lut_bits = dt->bits;
-    a.letters = static_cast<const uint8_t*>(ws.letters.p);
-    a.nleaves = static_cast<uint32_t>(dt->letters.size() / W);
-    a.width = W;
-    a.cu_count = wide_cu_count(static_cast<uint32_t>(ctx->cu_count));
     a.sub = d_sub;
     a.idx_off = d_idx_off;
     a.off = d_off;
@@ -144,6 +161,38 @@ Status wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, 
     a.out = d_out;
     a.status = d_status;
     HUFF_TRY(ctx->timed("wbatch_decode", [&] { return dev::launch_wbatch_decode(a, s); }));
+    return ctx->sync();
+}
+
+Status wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                            const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_idx_off,
+                            const uint64_t* d_off, const uint32_t* d_status_in, uint32_t nstreams,
+                            const uint32_t* d_req_stream, const uint64_t* d_req_first, const uint64_t* d_req_count,
+                            const uint64_t* d_req_out_begin, uint32_t nreq, uint8_t* d_out, size_t out_cap_letters,
+                            uint32_t* d_req_status) {
+    dev::WBatchRangesArgs a{};
+    HUFF_TRY(dec_check(t, d_out));
+    if (nreq == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    hipStream_t s = ctx->stream;
+    HUFF_TRY(dec_table(ctx, t, a));
+    a.comp = d_comp;
+    a.comp_off = d_comp_off;
+    a.bits = d_bits;
+    a.sub = d_sub;
+    a.idx_off = d_idx_off;
+    a.off = d_off;
+    a.status_in = d_status_in;
+    a.nstreams = nstreams;
+    a.req_stream = d_req_stream;
+    a.req_first = d_req_first;
+    a.req_count = d_req_count;
+    a.out_begin = d_req_out_begin;
+    a.nreq = nreq;
+    a.out = d_out;
+    a.out_cap = out_cap_letters;
+    a.status = d_req_status;
+    HUFF_TRY(ctx->timed("wbatch_decode_ranges", [&] { return dev::launch_wbatch_decode_ranges(a, s); }));
     return ctx->sync();
 }
 

@@ -96,6 +96,13 @@ Status wbatch_pack(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_in, cons
 Status wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
                      const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_idx_off, const uint64_t* d_off,
                      const uint32_t* d_status_in, uint32_t nstreams, uint8_t* d_out, uint32_t* d_status);
+// huff_wbatch_decode_ranges (device/wbatch_ranges.hip): the request arrays are device pointers too
+Status wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                            const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_idx_off,
+                            const uint64_t* d_off, const uint32_t* d_status_in, uint32_t nstreams,
+                            const uint32_t* d_req_stream, const uint64_t* d_req_first, const uint64_t* d_req_count,
+                            const uint64_t* d_req_out_begin, uint32_t nreq, uint8_t* d_out, size_t out_cap_letters,
+                            uint32_t* d_req_status);
 Status wcompress_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, size_t n, const huff_wtree* t,
                       huff_wcompress_data** out, u128* missing);
 Status wdecompress_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint8_t* out, size_t cap_letters,

@@ -209,6 +209,11 @@ SIGNATURES = [
     ("huff_diag_wbatch_builds", C.c_uint32, []),
     ("huff_diag_wbatch_build_name", C.c_char_p, [C.c_uint32]),
     ("huff_diag_wbatch_build_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_wbatch_decode_ranges", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, sz,
+                                      vp]),
+    ("huff_diag_wbatch_range_builds", C.c_uint32, []),
+    ("huff_diag_wbatch_range_build_name", C.c_char_p, [C.c_uint32]),
+    ("huff_diag_wbatch_range_build_launches", C.c_uint64, [C.c_uint32]),
 ]
 
 _lib = None
@@ -291,6 +296,14 @@ def wbatch_build_launches() -> dict:
     L = load()
     return {L.huff_diag_wbatch_build_name(k).decode(): L.huff_diag_wbatch_build_launches(k)
             for k in range(L.huff_diag_wbatch_builds())}
+
+
+def wbatch_range_build_launches() -> dict:
+    """{build name: launches so far} of huff_wbatch_decode_ranges' compiled builds
+    (huff_diag_wbatch_range_build_*): the nine k_wbatch_decode_ranges rows"""
+    L = load()
+    return {L.huff_diag_wbatch_range_build_name(k).decode(): L.huff_diag_wbatch_range_build_launches(k)
+            for k in range(L.huff_diag_wbatch_range_builds())}
 
 
 def last_error() -> str:

@@ -22,6 +22,14 @@ or call by call:
     wbatch_pack(ctx, tree, letters, offsets, bits, comp_off, idx_off, status, out, sub)
     status2 = wbatch_decode(ctx, tree, out, comp_off, bits, sub, idx_off, offsets, status, letters_out)
 
+Random access through the restart index, decoding only the 64-letter blocks a
+range touches (huff_wbatch_decode_ranges; first and count in letters):
+
+    letters, out_offsets, st = decompress_ranges(ctx, c, req_stream, req_first, req_count)
+    letters, out_offsets, st = decompress_streams(ctx, c, stream_ids)   # whole streams
+    st = wbatch_decode_ranges(ctx, tree, comp, comp_off, bits, sub, idx_off, offsets, status,
+                              req_stream, req_first, req_count, out_begin, out)
+
 A stream that cannot be coded gets a status (E_EMPTY_COMP for no letters,
 E_MISSING_LETTER with missing[s] = the index of the first letter without a
 code, E_INVALID_ARG for 2^32 bits or more) and owns no bytes; a stream that
@@ -37,7 +45,7 @@ import torch
 
 from . import _lib
 from ._lib import load
-from .batch import _dev, _p
+from .batch import _dev, _p, _req, _scan
 from .wide import I128, U128, LetterType, WideTree
 
 E_INVALID_ARG = _lib.E_INVALID_ARG
@@ -184,6 +192,48 @@ def wbatch_decode(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.T
     return status
 
 
+def wbatch_decode_ranges(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor,
+                         sub: torch.Tensor, index_offsets: torch.Tensor, offsets: torch.Tensor,
+                         status_in: torch.Tensor, req_stream: torch.Tensor, req_first: torch.Tensor,
+                         req_count: torch.Tensor, out_begin: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """huff_wbatch_decode_ranges: the letters [req_first[r], req_first[r] +
+    req_count[r]) of stream req_stream[r] to out[out_begin[r]:] (all in
+    letters), decoding only the 64-letter blocks they touch. req_stream is
+    int32 (u32 ids), the other three int64 (u64). Returns the per-request
+    status [R] (int32): see include/huffgpu_wide.h. sub None raises HuffError
+    (E_INVALID_ARG): a range needs the index. Output slots that overlap are the
+    caller's business."""
+    width = tree.ltype.width
+    ns = offsets.numel() - 1
+    assert ns >= 0
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(offsets, torch.int64)
+    _dev(status_in, torch.int32, (ns,))
+    _dev(index_offsets, torch.int64, (ns + 1,))
+    nreq = req_stream.numel()
+    _dev(req_stream, torch.int32, (nreq,))
+    _dev(req_first, torch.int64, (nreq,))
+    _dev(req_count, torch.int64, (nreq,))
+    _dev(out_begin, torch.int64, (nreq,))
+    if sub is not None:
+        _dev(sub, torch.int32)
+    cap = _letters(out, width)
+    # nothing reads outside comp or sub (the kernel keeps the slots inside cap): one host read
+    if nreq > 0 and ns > 0 and sub is not None:
+        ok = (comp_offsets.min() >= 0) & (comp_offsets.max() <= comp.numel())
+        ok &= (index_offsets.min() >= 0) & (index_offsets.max() <= sub.numel())
+        if not bool(ok.item()):
+            raise ValueError("offsets must lie inside their buffers")
+    status = torch.zeros(nreq, dtype=torch.int32, device=offsets.device)
+    _check(load().huff_wbatch_decode_ranges(ctx.h, tree.h, _p(comp), _p(comp_offsets), _p(bits), _p(sub),
+                                            _p(index_offsets), _p(offsets), _p(status_in), ns, _p(req_stream),
+                                            _p(req_first), _p(req_count), _p(out_begin), nreq, _p(out), cap,
+                                            _p(status)))
+    return status
+
+
 @dataclass
 class WideBatchCompressed:
     comp: torch.Tensor           # u8: the streams, tightly concatenated
@@ -224,3 +274,51 @@ def decompress_batch(ctx, c: WideBatchCompressed):
     status = wbatch_decode(ctx, c.tree, c.comp, c.comp_offsets, c.bits, c.sub, c.index_offsets, c.offsets, c.status,
                            out)
     return out, status
+
+
+def decompress_ranges(ctx, c: WideBatchCompressed, req_stream, req_first, req_count):
+    """(letters, out_offsets [R + 1] int64, status [R] int32): the letters
+    [req_first[r], req_first[r] + req_count[r]) of stream req_stream[r] of c,
+    in a tensor of c.letters_dtype (16-byte letters: uint8, 16 bytes per
+    letter), tightly concatenated in request order (out_offsets, in letters, is
+    the scan of the counts), through the restart index: one launch that decodes
+    only the 64-letter blocks the ranges touch, and two host reads. A request
+    whose status is not 0 (include/huffgpu_wide.h, huff_wbatch_decode_ranges)
+    keeps its slot, zero-filled."""
+    dev = c.comp.device
+    req_stream = _req(req_stream, torch.int32, dev)
+    req_first = _req(req_first, torch.int64, dev)
+    req_count = _req(req_count, torch.int64, dev)
+    nreq = req_stream.numel()
+    assert req_first.numel() == nreq and req_count.numel() == nreq
+    out_offsets = _scan(req_count)
+    per = c.width // torch.empty(0, dtype=c.letters_dtype).element_size()  # tensor elements per letter
+    if nreq == 0:
+        return (torch.zeros(0, dtype=c.letters_dtype, device=dev), out_offsets,
+                torch.zeros(0, dtype=torch.int32, device=dev))
+    lowest, total = torch.stack((req_count.min(), out_offsets[-1])).tolist()
+    if lowest < 0:
+        raise ValueError("req_count must not be negative")
+    out = torch.zeros(max(total, 1) * per, dtype=c.letters_dtype, device=dev)  # never a null pointer
+    status = wbatch_decode_ranges(ctx, c.tree, c.comp, c.comp_offsets, c.bits, c.sub, c.index_offsets, c.offsets,
+                                  c.status, req_stream, req_first, req_count, out_offsets[:-1].contiguous(), out)
+    out = out[: total * per]
+    bad = status != 0
+    if bool(bad.any().item()):  # a corrupt request may have written some of its letters
+        out[torch.repeat_interleave(bad, req_count * per, output_size=total * per)] = 0
+    return out, out_offsets, status
+
+
+def decompress_streams(ctx, c: WideBatchCompressed, stream_ids):
+    """decompress_ranges of the whole streams stream_ids[r] (first 0, count
+    n_s): (letters, out_offsets [R + 1], status [R]). An id outside the batch
+    owns no letters and gets E_INVALID_ARG."""
+    dev = c.comp.device
+    ids = _req(stream_ids, torch.int64, dev)
+    ns = c.offsets.numel() - 1
+    counts = torch.clamp(c.offsets[1:] - c.offsets[:-1], min=0)
+    valid = (ids >= 0) & (ids < ns)
+    req_count = torch.where(valid, counts[ids.clamp(0, max(ns - 1, 0))], torch.zeros_like(ids)) if ns > 0 \
+        else torch.zeros_like(ids)
+    req_stream = torch.where(valid, ids, torch.full_like(ids, ns)).to(torch.int32)
+    return decompress_ranges(ctx, c, req_stream, torch.zeros_like(ids), req_count)

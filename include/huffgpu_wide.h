@@ -360,6 +360,79 @@ int huff_wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp
                        const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams, void* d_out,
                        uint32_t* d_status);
 
+/* Letter ranges of chosen streams of such a batch through the restart index,
+ * in one launch (device pointers, the request arrays too, as for
+ * huff_batch_decode_ranges in huffgpu.h; synchronous on the context's stream;
+ * DESIGN.md §9, "Letter ranges of a wide batch"). The batch is described
+ * exactly as for huff_wbatch_decode. first, count, out_begin and
+ * out_cap_letters are in letters of the tree's width.
+ *  huff_wbatch_decode_ranges: request r asks for the letters [f, f + m) of
+ *                     stream s = d_req_stream[r], f = d_req_first[r], m =
+ *                     d_req_count[r], and gets them at d_out +
+ *                     d_req_out_begin[r] * width. Only the 64-letter blocks
+ *                     f / 64 .. (f + m - 1) / 64 of the stream are decoded,
+ *                     each one whole and under huff_wbatch_decode's rule:
+ *                     block j starts at d_sub[d_index_offsets[s] + j] and must
+ *                     end exactly at the next entry (the stream's last block:
+ *                     at d_bits[s]); entry 0 must be 0.
+ *                     d_req_status[r], the first that applies:
+ *                      HUFF_E_INVALID_ARG  s >= nstreams, or f + m overflows or
+ *                                          exceeds n_s, or out_begin + m
+ *                                          overflows or exceeds
+ *                                          out_cap_letters; nothing written.
+ *                      d_status_in[s]      if that is not HUFF_OK; nothing
+ *                                          written.
+ *                      HUFF_OK             m == 0: nothing read, nothing
+ *                                          written.
+ *                      HUFF_E_CORRUPT      the stream's own numbers disagree
+ *                                          (d_bits[s] >= 2^32, its bytes are
+ *                                          not ceil(d_bits[s] / 8), n_s >
+ *                                          d_bits[s], its index entries are
+ *                                          not ceil(n_s / 64)); nothing
+ *                                          written.
+ *                      HUFF_E_CORRUPT      a touched block has a window that
+ *                                          matches no code, a code crossing
+ *                                          its end, an end elsewhere, a first
+ *                                          entry other than 0, or an end past
+ *                                          d_bits[s]; only letters among the
+ *                                          request's own m output letters may
+ *                                          have been written.
+ *                      HUFF_OK             otherwise: exactly its m letters.
+ *                     A request reads only its stream's compressed bytes, the
+ *                     index entries of the blocks it touches and the one entry
+ *                     after them. Requests are independent, also on one
+ *                     stream: a bad entry j of the index makes exactly the
+ *                     requests that touch block j - 1 or block j corrupt.
+ *                     Output slots of different requests that overlap are the
+ *                     caller's business: each such letter gets one of the
+ *                     requests' letters. Before any device work:
+ *                     HUFF_E_INVALID_ARG when nreq > 0 and d_sub (a range needs
+ *                     the restart index) or any other pointer is NULL, or when
+ *                     d_out is not aligned to min(width, 16);
+ *                     HUFF_E_CODE_TOO_LONG for a tree with a code longer than 56
+ *                     bits. nreq == 0: HUFF_OK, no launch.
+ *
+ * One wave takes a request; a workgroup of 16 waves stages the tree's tables
+ * once and loops over requests, as huff_wbatch_decode does over streams.
+ * Cost, measured on an MI355X on huff_wbatch_decode's batches above
+ * (tools/wbatchrangebench.py, DESIGN.md §9, "Letter ranges of a wide batch";
+ * kernel times, medians of 10, one process, beside huff_wbatch_decode of the
+ * whole batch in the same process; 2- / 4-byte letters, Zipf then uniform):
+ * 256 letters of one stream in ten take 0.077 / 0.077 and 0.098 / 0.174 ms,
+ * 0.13 / 0.10 and 0.03 / 0.03 of the full decode; the whole of one stream in
+ * ten 0.162 / 0.172 and 0.522 / 1.333 ms, 0.28 / 0.22 and 0.18 / 0.20; 4,096
+ * letters of every stream, half of the batch, 0.309 / 0.373 and 1.278 / 3.421
+ * ms, 0.53 / 0.48 and 0.43 / 0.50. Every letter of
+ * every stream takes 0.99-1.04 of the full decode: short of the whole batch
+ * there is no share of it past which huff_wbatch_decode is the faster call;
+ * for the whole batch, make that call. */
+int huff_wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                              const uint64_t* d_bits, const uint32_t* d_sub, const uint64_t* d_index_offsets,
+                              const uint64_t* d_offsets, const uint32_t* d_status_in, uint32_t nstreams,
+                              const uint32_t* d_req_stream, const uint64_t* d_req_first, const uint64_t* d_req_count,
+                              const uint64_t* d_req_out_begin, uint32_t nreq, void* d_out, size_t out_cap_letters,
+                              uint32_t* d_req_status);
+
 /* ---------------- diagnostics (not reference functions) ------------------ */
 /* huff_wbatch_* take their kernels from tables of their own: 20 k_wbatch_bits
  * rows (letter width x u64 or u32 table values x table in LDS or read in
@@ -370,6 +443,14 @@ int huff_wbatch_decode(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp
 uint32_t huff_diag_wbatch_builds(void);
 const char* huff_diag_wbatch_build_name(uint32_t i);
 uint64_t huff_diag_wbatch_build_launches(uint32_t i);
+/* huff_wbatch_decode_ranges takes its kernel from a table of its own: 9
+ * k_wbatch_decode_ranges rows, letter type (uint8_t, uint16_t, uint32_t,
+ * uint64_t, U128) x leaf letters in LDS (true) or in global memory (false:
+ * more than 32 KiB of them), without <uint8_t, false>. Names and counts as
+ * huff_diag_wide_*. */
+uint32_t huff_diag_wbatch_range_builds(void);
+const char* huff_diag_wbatch_range_build_name(uint32_t i);
+uint64_t huff_diag_wbatch_range_build_launches(uint32_t i);
 /* The wide launchers take their kernels from tables of compiled builds: 20
  * k_wbits (pass 1), 32 k_wpack (pass 2), 30 k_wdec_task (codes <= 32 bits)
  * and 10 k_wdecode (longer codes) rows, enumerated in that order.
