@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "capi_util.hpp"
+#include "host/wbatch_index_plan.hpp"
 #include "huffgpu_wide.h"
 #include "runtime/wide_rt.hpp"
 
@@ -470,6 +471,36 @@ int huff_wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t*
                                           d_status_in, nstreams, d_req_stream, d_req_first, d_req_count,
                                           d_req_out_begin, nreq, static_cast<uint8_t*>(d_out), out_cap_letters,
                                           d_req_status);
+    });
+}
+
+size_t huff_wbatch_seg_entries(size_t total_comp_bytes, uint32_t nstreams) {
+    static_assert(HUFF_WBATCH_SEG_BITS == huff::kWBatchSegBits, "the header states the kernels' segment");
+    return static_cast<size_t>(huff::wbatch_seg_entries(total_comp_bytes, nstreams));
+}
+
+int huff_wbatch_count(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                      const uint64_t* d_bits, const uint32_t* d_status_in, uint32_t nstreams, uint64_t* d_seg,
+                      size_t seg_cap, uint64_t* d_counts, uint32_t* d_status) {
+    if (!ctx || !t || (nstreams && (!d_comp || !d_comp_offsets || !d_bits || !d_status_in || !d_seg || !d_counts ||
+                                    !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return huff::wbatch_count(ctx, t, d_comp, d_comp_offsets, d_bits, d_status_in, nstreams, d_seg, seg_cap,
+                                  d_counts, d_status);
+    });
+}
+
+int huff_wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                      const uint64_t* d_bits, const uint64_t* d_seg, size_t seg_cap, const uint64_t* d_offsets,
+                      const uint64_t* d_index_offsets, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub,
+                      size_t sub_cap) {
+    if (!ctx || !t || (nstreams && (!d_comp || !d_comp_offsets || !d_bits || !d_seg || !d_offsets ||
+                                    !d_index_offsets || !d_status || !d_sub)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return huff::wbatch_index(ctx, t, d_comp, d_comp_offsets, d_bits, d_seg, seg_cap, d_offsets, d_index_offsets,
+                                  d_status, nstreams, d_sub, sub_cap);
     });
 }
 

@@ -763,6 +763,50 @@ hipError_t launch_wbatch_decode_ranges(const WBatchRangesArgs& a, hipStream_t s)
 uint32_t wbatch_range_builds();
 const char* wbatch_range_build_name(uint32_t i);
 uint64_t wbatch_range_build_launches(uint32_t i);
+// The letter counts and the restart index of such a batch that came without
+// them (wbatch_index.hip; host/wbatch_index_plan.hpp): BatchCountArgs /
+// BatchIndexArgs with the tree's decode table in place of the code rows. Only
+// code lengths are looked up, so one build of each kernel serves every letter
+// width. One 256-lane workgroup per stream at a time, persistent: the primary
+// table is staged once per workgroup.
+struct WBatchCountArgs {
+    const uint8_t* comp;          // any alignment
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint32_t* lut;          // WideDecArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint8_t* letters;       // the tree's leaf letters: not read
+    uint32_t nleaves;
+    uint32_t width;
+    uint32_t cu_count;
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    uint64_t* seg;                // wbatch_seg_entries(total bytes, nstreams) entries at least
+    uint64_t seg_cap;
+    uint64_t* counts;             // [nstreams]: letters of the stream (0 unless kBatchOk)
+    uint32_t* status;             // status_in passed through, kBatchOk or kBatchCorrupt
+};
+struct WBatchIndexArgs {
+    const uint8_t* comp;          // any alignment
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint32_t* lut;          // WideDecArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint8_t* letters;       // the tree's leaf letters: not read
+    uint32_t nleaves;
+    uint32_t width;
+    uint32_t cu_count;
+    const uint64_t* seg;
+    uint64_t seg_cap;
+    const uint64_t* off;          // the letters' offsets: the scan of WBatchCountArgs::counts
+    const uint64_t* idx_off;      // the scan of ceil(counts / kWBatchBlock)
+    uint32_t* status;             // in and out: kBatchCorrupt where seg and off disagree
+    uint32_t nstreams;
+    uint32_t* sub;
+    uint64_t sub_cap;
+};
+hipError_t launch_wbatch_count(const WBatchCountArgs& a, hipStream_t s);
+hipError_t launch_wbatch_index(const WBatchIndexArgs& a, hipStream_t s);
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

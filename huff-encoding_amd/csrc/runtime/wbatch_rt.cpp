@@ -3,6 +3,7 @@
 // tree's tables come from huff_wtree::enc_tables() / dec_tables() as the
 // single-stream path builds them and live in buffers of the context, uploaded
 // when the tree changes.
+#include "../host/wbatch_index_plan.hpp"
 #include "wide_rt.hpp"
 
 #define HIP_TRY(expr) HIP_TRY_RT(expr)
@@ -193,6 +194,78 @@ Status wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d
     a.out_cap = out_cap_letters;
     a.status = d_req_status;
     HUFF_TRY(ctx->timed("wbatch_decode_ranges", [&] { return dev::launch_wbatch_decode_ranges(a, s); }));
+    return ctx->sync();
+}
+
+namespace {
+// what the count and the index refuse before any device work: a tree no wide
+// batch was ever packed with (dec_check's rule)
+Status wbatch_index_check(const huff_wtree* t) {
+    const WideDecTables* dt = nullptr;
+    HUFF_TRY(t->dec_tables(&dt));
+    if (dt->maxdepth > kWideMaxEncodeLen) return Status::err(HUFF_E_CODE_TOO_LONG, "code longer than 56 bits");
+    return Status::ok();
+}
+// one host read of a scan's total (the context is active)
+Status read_total(huff_ctx* ctx, const uint64_t* d_total, uint64_t& total) {
+    HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    return ctx->sync();
+}
+}  // namespace
+
+Status wbatch_count(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                    const uint64_t* d_bits, const uint32_t* d_status_in, uint32_t nstreams, uint64_t* d_seg,
+                    size_t seg_cap, uint64_t* d_counts, uint32_t* d_status) {
+    HUFF_TRY(wbatch_index_check(t));
+    if (nstreams == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    uint64_t total = 0;
+    HUFF_TRY(read_total(ctx, d_comp_off + nstreams, total));
+    if (wbatch_seg_entries(total, nstreams) > seg_cap)
+        return Status::err(HUFF_E_BUFFER_TOO_SMALL, "wide batch segment scratch too small");
+    dev::WBatchCountArgs a{};
+    HUFF_TRY(dec_table(ctx, t, a));
+    a.comp = d_comp;
+    a.comp_off = d_comp_off;
+    a.bits = d_bits;
+    a.status_in = d_status_in;
+    a.nstreams = nstreams;
+    a.seg = d_seg;
+    a.seg_cap = seg_cap;
+    a.counts = d_counts;
+    a.status = d_status;
+    hipStream_t s = ctx->stream;
+    HUFF_TRY(ctx->timed("wbatch_count", [&] { return dev::launch_wbatch_count(a, s); }));
+    return ctx->sync();
+}
+
+Status wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                    const uint64_t* d_bits, const uint64_t* d_seg, size_t seg_cap, const uint64_t* d_off,
+                    const uint64_t* d_idx_off, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub, size_t sub_cap) {
+    HUFF_TRY(wbatch_index_check(t));
+    if (nstreams == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    uint64_t total = 0, nsub = 0;
+    HUFF_TRY(read_total(ctx, d_comp_off + nstreams, total));
+    if (wbatch_seg_entries(total, nstreams) > seg_cap)
+        return Status::err(HUFF_E_BUFFER_TOO_SMALL, "wide batch segment scratch too small");
+    HUFF_TRY(read_total(ctx, d_idx_off + nstreams, nsub));
+    if (nsub > sub_cap) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "wide batch index capacity too small");
+    dev::WBatchIndexArgs a{};
+    HUFF_TRY(dec_table(ctx, t, a));
+    a.comp = d_comp;
+    a.comp_off = d_comp_off;
+    a.bits = d_bits;
+    a.seg = d_seg;
+    a.seg_cap = seg_cap;
+    a.off = d_off;
+    a.idx_off = d_idx_off;
+    a.status = d_status;
+    a.nstreams = nstreams;
+    a.sub = d_sub;
+    a.sub_cap = sub_cap;
+    hipStream_t s = ctx->stream;
+    HUFF_TRY(ctx->timed("wbatch_index", [&] { return dev::launch_wbatch_index(a, s); }));
     return ctx->sync();
 }
 

@@ -103,6 +103,14 @@ Status wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d
                             const uint32_t* d_req_stream, const uint64_t* d_req_first, const uint64_t* d_req_count,
                             const uint64_t* d_req_out_begin, uint32_t nreq, uint8_t* d_out, size_t out_cap_letters,
                             uint32_t* d_req_status);
+// huff_wbatch_count / _index (device/wbatch_index.hip): the letter counts and
+// the restart index of a batch that came without them
+Status wbatch_count(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                    const uint64_t* d_bits, const uint32_t* d_status_in, uint32_t nstreams, uint64_t* d_seg,
+                    size_t seg_cap, uint64_t* d_counts, uint32_t* d_status);
+Status wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                    const uint64_t* d_bits, const uint64_t* d_seg, size_t seg_cap, const uint64_t* d_off,
+                    const uint64_t* d_idx_off, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub, size_t sub_cap);
 Status wcompress_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, size_t n, const huff_wtree* t,
                       huff_wcompress_data** out, u128* missing);
 Status wdecompress_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint8_t* out, size_t cap_letters,

@@ -214,6 +214,9 @@ SIGNATURES = [
     ("huff_diag_wbatch_range_builds", C.c_uint32, []),
     ("huff_diag_wbatch_range_build_name", C.c_char_p, [C.c_uint32]),
     ("huff_diag_wbatch_range_build_launches", C.c_uint64, [C.c_uint32]),
+    ("huff_wbatch_seg_entries", sz, [sz, C.c_uint32]),
+    ("huff_wbatch_count", i, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, vp]),
+    ("huff_wbatch_index", i, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, sz]),
 ]
 
 _lib = None

@@ -30,6 +30,18 @@ range touches (huff_wbatch_decode_ranges; first and count in letters):
     st = wbatch_decode_ranges(ctx, tree, comp, comp_off, bits, sub, idx_off, offsets, status,
                               req_stream, req_first, req_count, out_begin, out)
 
+Streams that came from elsewhere, without letter counts and without an index
+(the reference's compress_with_tree under one shared tree, or a batch packed in
+another process whose index was not shipped), become such a batch by two
+launches, huff_wbatch_count and huff_wbatch_index, codes of 33-56 bits included:
+
+    c = WideBatchCompressed.from_streams(ctx, tree, comp, comp_offsets, bits=bits)   # or padding=...
+    c = WideBatchCompressed.from_compress_data(ctx, [wide.WideCompressData, ...])    # one shared tree
+    cds = c.to_compress_data()                                                       # and back, on the host
+    seg = torch.empty(wbatch_seg_entries(comp.numel(), S), dtype=torch.int64, device="cuda")
+    counts, status = wbatch_count(ctx, tree, comp, comp_offsets, bits, status_in, seg)
+    wbatch_index(ctx, tree, comp, comp_offsets, bits, seg, offsets, index_offsets, status, sub)
+
 A stream that cannot be coded gets a status (E_EMPTY_COMP for no letters,
 E_MISSING_LETTER with missing[s] = the index of the first letter without a
 code, E_INVALID_ARG for 2^32 bits or more) and owns no bytes; a stream that
@@ -46,7 +58,7 @@ import torch
 from . import _lib
 from ._lib import load
 from .batch import _dev, _p, _req, _scan
-from .wide import I128, U128, LetterType, WideTree
+from .wide import I128, U128, LetterType, WideCompressData, WideTree
 
 E_INVALID_ARG = _lib.E_INVALID_ARG
 E_MISSING_LETTER = _lib.E_MISSING_LETTER
@@ -234,6 +246,64 @@ def wbatch_decode_ranges(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: 
     return status
 
 
+def wbatch_seg_entries(total_comp_bytes: int, nstreams: int) -> int:
+    """huff_wbatch_seg_entries: the int64 entries of scratch wbatch_count and wbatch_index share"""
+    return int(load().huff_wbatch_seg_entries(total_comp_bytes, nstreams))
+
+
+def _never_null(t: torch.Tensor) -> torch.Tensor:
+    """t, or one element of its kind where t is empty: the C calls refuse null pointers"""
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def wbatch_count(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor,
+                 status_in: torch.Tensor, seg: torch.Tensor):
+    """huff_wbatch_count: (counts [S] int64, status [S] int32) of the streams
+    comp[comp_offsets[s]:comp_offsets[s + 1]] of bits[s] valid bits under
+    `tree`; seg (int64 scratch of wbatch_seg_entries(comp.numel(), S) entries
+    at least, its numel is the capacity) is filled for wbatch_index. Raises
+    HuffError (E_BUFFER_TOO_SMALL) if seg is short."""
+    ns = status_in.numel()
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(status_in, torch.int32, (ns,))
+    _dev(seg, torch.int64)
+    _offsets_inside(comp_offsets, comp.numel(), "comp_offsets")
+    counts = torch.zeros(ns, dtype=torch.int64, device=status_in.device)
+    status = torch.zeros(ns, dtype=torch.int32, device=status_in.device)
+    _check(load().huff_wbatch_count(ctx.h, tree.h, _p(_never_null(comp)), _p(comp_offsets), _p(bits), _p(status_in), ns,
+                                    _p(_never_null(seg)), seg.numel(), _p(counts), _p(status)))
+    return counts, status
+
+
+def wbatch_index(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor,
+                 seg: torch.Tensor, offsets: torch.Tensor, index_offsets: torch.Tensor, status: torch.Tensor,
+                 sub: torch.Tensor) -> None:
+    """huff_wbatch_index into sub (int32 holding u32 offsets, its numel is the
+    capacity): the bit offset of every 64th letter of every stream, from seg as
+    wbatch_count left it, offsets = the scan of the counts and index_offsets =
+    the scan of ceil(counts / 64). status is updated in place (E_CORRUPT where
+    seg, offsets and index_offsets disagree). Raises HuffError
+    (E_BUFFER_TOO_SMALL) with nothing written if seg or sub is short."""
+    ns = status.numel()
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(seg, torch.int64)
+    _dev(offsets, torch.int64, (ns + 1,))
+    _dev(index_offsets, torch.int64, (ns + 1,))
+    _dev(status, torch.int32, (ns,))
+    _dev(sub, torch.int32)
+    _offsets_inside(comp_offsets, comp.numel(), "comp_offsets")
+    _check(load().huff_wbatch_index(ctx.h, tree.h, _p(_never_null(comp)), _p(comp_offsets), _p(bits),
+                                    _p(_never_null(seg)), seg.numel(), _p(offsets), _p(index_offsets), _p(status), ns,
+                                    _p(_never_null(sub)), sub.numel()))
+
+
+_TORCH_OF_WIDTH = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64, 16: torch.uint8}
+
+
 @dataclass
 class WideBatchCompressed:
     comp: torch.Tensor           # u8: the streams, tightly concatenated
@@ -247,6 +317,91 @@ class WideBatchCompressed:
     tree: WideTree
     width: int
     letters_dtype: torch.dtype = torch.uint8  # the tensor type decompress_batch returns letters in
+
+    @staticmethod
+    def from_streams(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor = None,
+                     padding: torch.Tensor = None, letters_dtype: torch.dtype = None) -> "WideBatchCompressed":
+        """The batch of the streams comp[comp_offsets[s]:comp_offsets[s + 1]]
+        (u8, tight, any alignment) that `tree` coded, which came without letter
+        counts and without an index. Exactly one of bits ([S] int64: the valid
+        bits) and padding ([S] uint8, 0..7: bits = 8 * bytes - padding) is
+        given. huff_wbatch_count, two scans, one host read of the index total,
+        huff_wbatch_index. decompress_batch, decompress_ranges and
+        decompress_streams take the result; a stream that does not end at a
+        code boundary has E_CORRUPT and no letters, a stream of no bytes has
+        status 0 and no letters. letters_dtype: the tensor type letters are
+        returned in (default: the tree's width as uint8 / int16 / int32 /
+        int64; 16-byte letters as uint8)."""
+        if (bits is None) == (padding is None):
+            raise ValueError("give exactly one of bits and padding")
+        width = tree.ltype.width
+        ns = comp_offsets.numel() - 1
+        assert ns >= 0
+        _dev(comp, torch.uint8)
+        _dev(comp_offsets, torch.int64, (ns + 1,))
+        dev = comp_offsets.device
+        if bits is None:
+            _dev(padding, torch.uint8, (ns,))
+            if ns and int(padding.max().item()) > 7:
+                raise ValueError("padding must be 0..7")
+            bits = (comp_offsets[1:] - comp_offsets[:-1]) * 8 - padding.to(torch.int64)
+        _dev(bits, torch.int64, (ns,))
+        if letters_dtype is None:
+            letters_dtype = _TORCH_OF_WIDTH[width]
+        elif torch.empty(0, dtype=letters_dtype).element_size() not in (1, width):
+            raise TypeError(f"{letters_dtype} does not hold letters of {width} bytes")
+        seg = torch.empty(wbatch_seg_entries(comp.numel(), ns), dtype=torch.int64, device=dev)
+        counts, status = wbatch_count(ctx, tree, comp, comp_offsets, bits, torch.zeros(ns, dtype=torch.int32, device=dev),
+                                      seg)
+        offsets = _scan(counts)
+        index_offsets = _scan((counts + (IDX - 1)) // IDX)
+        sub = torch.empty(int(index_offsets[-1].item()), dtype=torch.int32, device=dev)
+        wbatch_index(ctx, tree, comp, comp_offsets, bits, seg, offsets, index_offsets, status, sub)
+        missing = torch.full((ns,), -1, dtype=torch.int64, device=dev)
+        return WideBatchCompressed(comp, comp_offsets, bits, sub, index_offsets, status, missing, offsets, tree, width,
+                                   letters_dtype)
+
+    @staticmethod
+    def from_compress_data(ctx, cds) -> "WideBatchCompressed":
+        """from_streams of a list of wide.WideCompressData (from
+        try_from_bytes of reference-written containers, say) that all hold the
+        same tree: the same as_bin() and letter type, else ValueError. The
+        payloads are concatenated on the host and uploaded once."""
+        cds = list(cds)
+        if not cds:
+            raise ValueError("no streams")
+        tree = cds[0].huff_tree()
+        shape = tree.as_bin()
+        for cd in cds[1:]:
+            if cd.ltype.name != tree.ltype.name or cd.huff_tree().as_bin() != shape:
+                raise ValueError("the streams of a wide batch share one tree")
+        payloads = [cd.comp_bytes() for cd in cds]
+        sizes = np.asarray([len(b) for b in payloads], np.int64)
+        coff = np.zeros(len(cds) + 1, np.int64)
+        coff[1:] = np.cumsum(sizes)
+        flat = np.frombuffer(b"".join(payloads), np.uint8)
+        dev = torch.device("cuda")
+        comp = torch.from_numpy(flat.copy()).to(dev)
+        padding = torch.from_numpy(np.asarray([cd.padding_bits() for cd in cds], np.uint8)).to(dev)
+        return WideBatchCompressed.from_streams(ctx, tree, comp, torch.from_numpy(coff).to(dev), padding=padding)
+
+    def to_compress_data(self):
+        """[wide.WideCompressData.new(bytes, padding, tree) for every stream
+        whose status is 0, None for the others] (a stream of no bytes: None, a
+        CompressData is never empty): one download of the bytes, one of the
+        per-stream numbers."""
+        ns = self.status.numel()
+        nums = torch.cat((self.comp_offsets, self.bits, self.status.to(torch.int64))).cpu().numpy()
+        coff, bits, status = nums[: ns + 1], nums[ns + 1: 2 * ns + 1], nums[2 * ns + 1:]
+        comp = self.comp.cpu().numpy().tobytes()
+        out = []
+        for s in range(ns):
+            lo, hi = int(coff[s]), int(coff[s + 1])
+            if status[s] != 0 or hi <= lo:
+                out.append(None)
+                continue
+            out.append(WideCompressData.new(comp[lo:hi], int((8 - int(bits[s]) % 8) % 8), self.tree))
+        return out
 
 
 def compress_batch(ctx, letters: torch.Tensor, offsets: torch.Tensor, tree: WideTree) -> WideBatchCompressed:

@@ -433,6 +433,95 @@ int huff_wbatch_decode_ranges(huff_ctx* ctx, const huff_wtree* t, const uint8_t*
                               const uint64_t* d_req_out_begin, uint32_t nreq, void* d_out, size_t out_cap_letters,
                               uint32_t* d_req_status);
 
+/* The letter counts and the restart index of such a batch that came WITHOUT
+ * them: streams the reference's compress_with_tree wrote under one shared tree,
+ * or a batch huff_wbatch_pack wrote elsewhere whose index was not shipped
+ * (huff_batch_count / huff_batch_index in huffgpu.h, with the tree in place of
+ * d_codes; DESIGN.md §9, "Streams that come without counts"). Device pointers,
+ * synchronous on the context's stream. Stream s is the bytes
+ * [d_comp_offsets[s], d_comp_offsets[s + 1]) of d_comp (any alignment, the
+ * streams tight) and d_bits[s] its valid bits, 8 * bytes - padding. After
+ * count, the two scans of d_counts and of ceil(d_counts / 64) (nstreams + 1
+ * entries each: d_offsets, d_index_offsets) and index, huff_wbatch_decode and
+ * huff_wbatch_decode_ranges take the batch as one this library packed. Codes of
+ * up to 56 bits are taken, the 33- to 56-bit ones that huff_dev_wdecompress
+ * refuses without an index included.
+ *
+ *  huff_wbatch_seg_entries: host only. The u64 entries of scratch (d_seg) the
+ *                      two calls share: one per HUFF_WBATCH_SEG_BITS-bit segment
+ *                      of every stream; stream s owns the entries from
+ *                      d_comp_offsets[s] / (HUFF_WBATCH_SEG_BITS / 8) + s, which
+ *                      needs no scan and keeps the streams' ranges disjoint, so
+ *                      the answer is total_comp_bytes / (HUFF_WBATCH_SEG_BITS /
+ *                      8) + nstreams.
+ *  huff_wbatch_count:  d_counts[s] = the letters the reference's decompress
+ *                      (comp.rs:487-519) yields for the stream under t; d_seg
+ *                      gets, per segment, the first code boundary at or past
+ *                      the segment's start (low 32 bits) and the letters before
+ *                      it (high 32 bits). d_status[s], the first that applies:
+ *                       d_status_in[s]   if that is not HUFF_OK; the count is 0
+ *                                        and nothing of the stream is read.
+ *                       HUFF_E_CORRUPT   d_bits[s] >= 2^32, bytes other than
+ *                                        ceil(d_bits[s] / 8), or segments that
+ *                                        do not fit seg_cap; count 0.
+ *                       HUFF_OK          a stream of 0 bits: count 0.
+ *                       HUFF_E_CORRUPT   a window matches no code (no huff_wtree
+ *                                        has such a table; the walk ends there
+ *                                        all the same), or the last code
+ *                                        crosses d_bits[s]; count 0.
+ *                       HUFF_OK          otherwise.
+ *                      The last rule is huff_wbatch_decode's, and it DIVERGES
+ *                      from huff_wcd_build_index, which drops a trailing
+ *                      incomplete code as the reference's decompress does:
+ *                      a batch stream must end at a code boundary, as
+ *                      huff_batch_count documents for bytes.
+ *  huff_wbatch_index:  d_sub[d_index_offsets[s] + j] = the bit offset of letter
+ *                      64 j of stream s: huff_wbatch_pack's index, entry for
+ *                      entry. d_status is read and updated: a stream that is
+ *                      not HUFF_OK is skipped; it becomes HUFF_E_CORRUPT where
+ *                      the segments do not chain from (bit 0, letter 0) to
+ *                      (d_bits[s], n_s), or where the stream's entry range is
+ *                      not ceil(n_s / 64) or leaves sub_cap. Reads the index
+ *                      total back first and returns HUFF_E_BUFFER_TOO_SMALL
+ *                      with nothing written if sub_cap (entries) is short.
+ *  Both, before any device work: HUFF_E_INVALID_ARG for a null pointer,
+ *  HUFF_E_CODE_TOO_LONG for a tree with a code longer than 56 bits; nstreams =
+ *  0: HUFF_OK, no launch. Then HUFF_E_BUFFER_TOO_SMALL if seg_cap <
+ *  huff_wbatch_seg_entries(d_comp_offsets[nstreams], nstreams) (one host read).
+ *
+ * A stream, whatever d_bits or the offsets claim, reads only its own compressed
+ * bytes and writes only its own segment entries, d_counts[s], d_status[s] and
+ * its own d_sub entries: one bad stream leaves its neighbours alone.
+ *
+ * Two launches for the whole batch. A 256-lane workgroup stages the tree's
+ * primary decode table once and loops over streams; a stream is cut into
+ * 256-bit segments, 256 per round, whose lanes walk from guessed entries and
+ * again from their predecessor's exit until nothing changes (at most 256
+ * times). Only code lengths are looked up: one kernel serves every letter
+ * width.
+ * Cost, measured on an MI355X on huff_wbatch_decode's batches above
+ * (tools/wbatchindexbench.py, DESIGN.md §9, "Streams that come without counts";
+ * kernel times, medians of 10, one process, beside huff_wbatch_decode of the
+ * same batch; 2- / 4-byte letters, Zipf then uniform): the count takes 0.86 /
+ * 0.86 and 0.40 / 239 ms, the index 0.41 / 0.42 and 0.41 / 2.2 ms, together
+ * 2.2 / 1.6 and 0.27 / 35 times one huff_wbatch_decode. Codes that are all 16
+ * bits divide the segment and every guess is right; THE 19-21-BIT CODES OF 2^20
+ * EQUALLY LIKELY LETTERS NEVER RESYNCHRONISE, the truth advances one segment
+ * per pass and every code is two dependent reads of L2. With the allocations,
+ * the scans and the decode (from_streams + decompress_batch) the batch's
+ * letters take 2.4-247 ms of wall time against 3.4-2,375 s for one
+ * huff_wenc_from_stream job and decode per stream (extrapolated from 200
+ * streams): 1,300-9,600 times faster. */
+#define HUFF_WBATCH_SEG_BITS 256
+size_t huff_wbatch_seg_entries(size_t total_comp_bytes, uint32_t nstreams);
+int huff_wbatch_count(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                      const uint64_t* d_bits, const uint32_t* d_status_in, uint32_t nstreams, uint64_t* d_seg,
+                      size_t seg_cap, uint64_t* d_counts, uint32_t* d_status);
+int huff_wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                      const uint64_t* d_bits, const uint64_t* d_seg, size_t seg_cap, const uint64_t* d_offsets,
+                      const uint64_t* d_index_offsets, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub,
+                      size_t sub_cap);
+
 /* ---------------- diagnostics (not reference functions) ------------------ */
 /* huff_wbatch_* take their kernels from tables of their own: 20 k_wbatch_bits
  * rows (letter width x u64 or u32 table values x table in LDS or read in
