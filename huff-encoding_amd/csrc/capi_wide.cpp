@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "capi_util.hpp"
+#include "host/wbatch_blob.hpp"
 #include "host/wbatch_index_plan.hpp"
 #include "huffgpu_wide.h"
 #include "runtime/wide_rt.hpp"
@@ -503,6 +504,61 @@ int huff_wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp,
                                   d_status, nstreams, d_sub, sub_cap);
     });
 }
+
+int huff_wbatch_blob_size(const huff_wtree* t, uint32_t nstreams, size_t comp_bytes, size_t nsub, int with_index,
+                          size_t* size) {
+    if (!t || !size) return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] { return huff::wbatch_blob_size(t, nstreams, comp_bytes, nsub, with_index != 0, size); });
+}
+
+int huff_wbatch_to_bytes(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                         const uint64_t* d_bits, const uint32_t* d_status, const uint64_t* d_offsets,
+                         const uint32_t* d_sub, const uint64_t* d_index_offsets, uint32_t nstreams, int with_index,
+                         uint8_t* out, size_t cap, size_t* out_len) {
+    if (!ctx || !t || !out_len || (!out && cap) || (nstreams && (!d_comp || !d_comp_offsets || !d_bits || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    if (with_index && nstreams && (!d_sub || !d_offsets || !d_index_offsets))
+        return fail(HUFF_E_INVALID_ARG, "null argument: the index needs d_sub, d_offsets and d_index_offsets");
+    return guarded([&] {
+        return huff::wbatch_to_bytes(ctx, t, d_comp, d_comp_offsets, d_bits, d_status, d_offsets, d_sub, d_index_offsets,
+                                     nstreams, with_index != 0, out, cap, out_len);
+    });
+}
+
+int huff_wbatch_blob_parse(const uint8_t* blob, size_t len, huff_wbatch_blob_view* view) {
+    if (!view || (!blob && len)) return fail(HUFF_E_INVALID_ARG, "null argument");
+    huff::WBatchBlobView v;
+    const huff::WBatchBlobError e = huff::wbatch_blob_parse(blob, len, &v);
+    if (e != huff::WBatchBlobError::Ok) return fail(HUFF_E_FROM_BYTES, huff::wbatch_blob_error_text(e));
+    *view = huff_wbatch_blob_view{};
+    view->width = v.width;
+    view->nstreams = v.nstreams;
+    view->has_index = v.has_index;
+    view->tree_nbits = v.tree_nbits;
+    view->comp_bytes = v.comp_bytes;
+    view->nsub = v.nsub;
+    view->tree_off = v.tree_off;
+    view->bits_off = v.bits_off;
+    view->counts_off = v.counts_off;
+    view->sub_off = v.sub_off;
+    view->comp_off = v.comp_off;
+    return HUFF_OK;
+}
+
+int huff_wbatch_verify(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                       const uint64_t* d_comp_offsets, const uint64_t* d_bits, const uint32_t* d_sub, size_t sub_entries,
+                       const uint64_t* d_index_offsets, const uint64_t* d_offsets, const uint32_t* d_status_in,
+                       uint32_t nstreams, uint32_t* d_status) {
+    if (!ctx || !t || (nstreams && (!d_comp || !d_comp_offsets || !d_bits || !d_sub || !d_index_offsets || !d_offsets ||
+                                    !d_status_in || !d_status)))
+        return fail(HUFF_E_INVALID_ARG, "null argument");
+    return guarded([&] {
+        return huff::wbatch_verify(ctx, t, d_comp, comp_bytes, d_comp_offsets, d_bits, d_sub, sub_entries,
+                                   d_index_offsets, d_offsets, d_status_in, nstreams, d_status);
+    });
+}
+
+uint64_t huff_diag_wbatch_verify_launches(void) { return huff::dev::wbatch_verify_launches(); }
 
 uint32_t huff_diag_wbatch_builds(void) { return huff::dev::wbatch_builds(); }
 const char* huff_diag_wbatch_build_name(uint32_t i) { return huff::dev::wbatch_build_name(i); }

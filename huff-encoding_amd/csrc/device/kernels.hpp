@@ -807,6 +807,34 @@ struct WBatchIndexArgs {
 };
 hipError_t launch_wbatch_count(const WBatchCountArgs& a, hipStream_t s);
 hipError_t launch_wbatch_index(const WBatchIndexArgs& a, hipStream_t s);
+// The proof of such a batch's letter counts and restart index against its
+// streams, for arrays that came from elsewhere (wbatch_verify.hip;
+// host/wbatch_blob.hpp): WBatchDecArgs without an output. Every block's
+// min(64, n_s - 64 j) codes must run from its entry exactly to the next; only
+// code lengths are looked up, no leaf letter is read and nothing but status[s]
+// is written, so one build serves every letter width. k_wbatch_decode's
+// geometry: a wave per stream, a lane per block, persistent workgroups.
+struct WBatchVerifyArgs {
+    const uint8_t* comp;          // any alignment
+    uint64_t comp_bytes;          // no stream's bytes may leave [0, comp_bytes)
+    const uint64_t* comp_off;
+    const uint64_t* bits;
+    const uint32_t* sub;
+    uint64_t sub_entries;         // no stream's entries may leave [0, sub_entries)
+    const uint64_t* idx_off;
+    const uint64_t* off;          // the letters' offsets: n_s = off[s + 1] - off[s]
+    const uint32_t* lut;          // WideDecArgs::lut
+    uint32_t lut_bits;            // <= kLutMaxBits
+    const uint8_t* letters;       // the tree's leaf letters: not read
+    uint32_t nleaves;
+    uint32_t width;
+    uint32_t cu_count;
+    const uint32_t* status_in;
+    uint32_t nstreams;
+    uint32_t* status;             // status_in passed through, kBatchOk or kBatchCorrupt
+};
+hipError_t launch_wbatch_verify(const WBatchVerifyArgs& a, hipStream_t s);
+uint64_t wbatch_verify_launches();
 hipError_t launch_indexless_spec(const IndexlessArgs& a, hipStream_t s);
 // LDS-staged path: k_fix_list (round 0 over the segments that can differ)
 // then k_fix_chain (one workgroup following the changed exits, a no-op when

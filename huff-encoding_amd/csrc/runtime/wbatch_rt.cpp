@@ -3,6 +3,9 @@
 // tree's tables come from huff_wtree::enc_tables() / dec_tables() as the
 // single-stream path builds them and live in buffers of the context, uploaded
 // when the tree changes.
+#include <vector>
+
+#include "../host/wbatch_blob.hpp"
 #include "../host/wbatch_index_plan.hpp"
 #include "wide_rt.hpp"
 
@@ -266,6 +269,124 @@ Status wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, c
     a.sub_cap = sub_cap;
     hipStream_t s = ctx->stream;
     HUFF_TRY(ctx->timed("wbatch_index", [&] { return dev::launch_wbatch_index(a, s); }));
+    return ctx->sync();
+}
+
+Status wbatch_blob_size(const huff_wtree* t, uint32_t nstreams, uint64_t comp_bytes, uint64_t nsub, bool with_index,
+                        size_t* size) {
+    if (!with_index && nsub != 0) return Status::err(HUFF_E_INVALID_ARG, "index entries without the index");
+    WBatchBlobView v;
+    if (!wbatch_blob_layout(t->t.as_bin().size(), nstreams, comp_bytes, nsub, with_index, &v) ||
+        v.size > static_cast<uint64_t>(SIZE_MAX))
+        return Status::err(HUFF_E_INVALID_ARG, "the wide batch container's size does not fit");
+    *size = static_cast<size_t>(v.size);
+    return Status::ok();
+}
+
+namespace {
+// consecutive device ranges that land one after another in the output leave in one copy
+struct CopyRun {
+    uint64_t src, dst, len;
+};
+void add_run(std::vector<CopyRun>& runs, uint64_t src, uint64_t dst, uint64_t len) {
+    if (len == 0) return;
+    if (!runs.empty() && runs.back().src + runs.back().len == src && runs.back().dst + runs.back().len == dst)
+        runs.back().len += len;
+    else
+        runs.push_back({src, dst, len});
+}
+}  // namespace
+
+Status wbatch_to_bytes(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                       const uint64_t* d_bits, const uint32_t* d_status, const uint64_t* d_off, const uint32_t* d_sub,
+                       const uint64_t* d_idx_off, uint32_t nstreams, bool with_index, uint8_t* out, size_t cap,
+                       size_t* out_len) {
+    HUFF_TRY(wbatch_index_check(t));
+    const std::vector<uint8_t> tree_bits = t->t.as_bin();
+    const std::vector<uint8_t> tree_packed = pack_msb0(tree_bits);
+    const size_t ns = nstreams;
+    // the per-stream numbers, in one host buffer: comp_off | bits | status | off | idx_off
+    std::vector<uint64_t> coff(ns + 1, 0), bits(ns, 0), off(ns + 1, 0), ioff(ns + 1, 0), counts(ns, 0);
+    std::vector<uint32_t> status(ns, 0);
+    if (ns) {
+        HUFF_TRY(ctx->activate());
+        hipStream_t s = ctx->stream;
+        HIP_TRY(hipMemcpyAsync(coff.data(), d_comp_off, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(bits.data(), d_bits, ns * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(status.data(), d_status, ns * 4, hipMemcpyDeviceToHost, s));
+        if (with_index) {
+            HIP_TRY(hipMemcpyAsync(off.data(), d_off, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(ioff.data(), d_idx_off, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
+        }
+        HUFF_TRY(ctx->sync());
+    }
+    // a stream that is not HUFF_OK is stored as a stream of nothing: its bytes
+    // (none, from huff_wbatch_bits) and the entries reserved for it are dropped
+    std::vector<CopyRun> comp_runs, sub_runs;
+    uint64_t comp_bytes = 0, nsub = 0;
+    for (size_t k = 0; k < ns; ++k) {
+        if (status[k] != HUFF_OK) {
+            bits[k] = 0;
+            continue;
+        }
+        const uint64_t c0 = coff[k], c1 = coff[k + 1];
+        if ((bits[k] >> 32) != 0 || c1 < c0 || c1 - c0 != wbatch_blob_bytes_of_bits(bits[k]))
+            return Status::err(HUFF_E_INVALID_ARG, "a stream's bytes are not ceil(bits / 8): not a tight wide batch");
+        add_run(comp_runs, c0, comp_bytes, c1 - c0);
+        comp_bytes += c1 - c0;
+        if (!with_index) continue;
+        const uint64_t n = wbatch_letters(off[k], off[k + 1]);
+        const uint64_t i0 = ioff[k], i1 = ioff[k + 1];
+        if (i1 < i0 || i1 - i0 != wbatch_blocks(n))
+            return Status::err(HUFF_E_INVALID_ARG, "a stream's index entries are not ceil(n / 64): not a tight wide batch");
+        counts[k] = n;
+        add_run(sub_runs, i0, nsub, i1 - i0);
+        nsub += i1 - i0;
+    }
+    WBatchBlobView v;
+    if (!wbatch_blob_layout(tree_bits.size(), nstreams, comp_bytes, nsub, with_index, &v) ||
+        v.size > static_cast<uint64_t>(SIZE_MAX))
+        return Status::err(HUFF_E_INVALID_ARG, "the wide batch container's size does not fit");
+    v.width = t->t.width();
+    *out_len = static_cast<size_t>(v.size);
+    if (!out && cap == 0) return Status::ok();  // the size was asked for
+    if (cap < v.size) return Status::err(HUFF_E_BUFFER_TOO_SMALL, "output buffer too small");
+    if (!out) return Status::err(HUFF_E_INVALID_ARG, "null argument");
+    wbatch_blob_write_head(v, tree_packed.data(), bits.data(), counts.data(), out);
+    // the entries are little-endian u32 on the device as in the blob
+    if (!comp_runs.empty() || !sub_runs.empty()) {
+        hipStream_t s = ctx->stream;
+        for (const CopyRun& r : sub_runs)
+            HIP_TRY(hipMemcpyAsync(out + v.sub_off + 4 * r.dst, d_sub + r.src, 4 * r.len, hipMemcpyDeviceToHost, s));
+        for (const CopyRun& r : comp_runs)
+            HIP_TRY(hipMemcpyAsync(out + v.comp_off + r.dst, d_comp + r.src, r.len, hipMemcpyDeviceToHost, s));
+        HUFF_TRY(ctx->sync());
+    }
+    return Status::ok();
+}
+
+Status wbatch_verify(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                     const uint64_t* d_comp_off, const uint64_t* d_bits, const uint32_t* d_sub, size_t sub_entries,
+                     const uint64_t* d_idx_off, const uint64_t* d_off, const uint32_t* d_status_in, uint32_t nstreams,
+                     uint32_t* d_status) {
+    HUFF_TRY(wbatch_index_check(t));
+    if (nstreams == 0) return Status::ok();
+    HUFF_TRY(ctx->activate());
+    dev::WBatchVerifyArgs a{};
+    HUFF_TRY(dec_table(ctx, t, a));
+    a.comp = d_comp;
+    a.comp_bytes = comp_bytes;
+    a.comp_off = d_comp_off;
+    a.bits = d_bits;
+    a.sub = d_sub;
+    a.sub_entries = sub_entries;
+    a.idx_off = d_idx_off;
+    a.off = d_off;
+    a.status_in = d_status_in;
+    a.nstreams = nstreams;
+    a.status = d_status;
+    hipStream_t s = ctx->stream;
+    HUFF_TRY(ctx->timed("wbatch_verify", [&] { return dev::launch_wbatch_verify(a, s); }));
     return ctx->sync();
 }
 

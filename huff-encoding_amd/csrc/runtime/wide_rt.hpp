@@ -111,6 +111,19 @@ Status wbatch_count(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, c
 Status wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
                     const uint64_t* d_bits, const uint64_t* d_seg, size_t seg_cap, const uint64_t* d_off,
                     const uint64_t* d_idx_off, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub, size_t sub_cap);
+// huff_wbatch_blob_size / _to_bytes / _verify (host/wbatch_blob.hpp,
+// device/wbatch_verify.hip): a whole batch as one container, and the proof of
+// its counts and index on the way back
+Status wbatch_blob_size(const huff_wtree* t, uint32_t nstreams, uint64_t comp_bytes, uint64_t nsub, bool with_index,
+                        size_t* size);
+Status wbatch_to_bytes(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_off,
+                       const uint64_t* d_bits, const uint32_t* d_status, const uint64_t* d_off, const uint32_t* d_sub,
+                       const uint64_t* d_idx_off, uint32_t nstreams, bool with_index, uint8_t* out, size_t cap,
+                       size_t* out_len);
+Status wbatch_verify(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                     const uint64_t* d_comp_off, const uint64_t* d_bits, const uint32_t* d_sub, size_t sub_entries,
+                     const uint64_t* d_idx_off, const uint64_t* d_off, const uint32_t* d_status_in, uint32_t nstreams,
+                     uint32_t* d_status);
 Status wcompress_host(huff_ctx* ctx, uint32_t width, const uint8_t* letters, size_t n, const huff_wtree* t,
                       huff_wcompress_data** out, u128* missing);
 Status wdecompress_host(huff_ctx* ctx, const huff_wcompress_data* cd, uint8_t* out, size_t cap_letters,

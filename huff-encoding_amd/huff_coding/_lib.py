@@ -217,7 +217,25 @@ SIGNATURES = [
     ("huff_wbatch_seg_entries", sz, [sz, C.c_uint32]),
     ("huff_wbatch_count", i, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, sz, vp, vp]),
     ("huff_wbatch_index", i, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, sz]),
+    ("huff_wbatch_blob_size", i, [vp, C.c_uint32, sz, sz, i, szp]),
+    ("huff_wbatch_to_bytes", i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, i, vp, sz, vp]),
+    ("huff_wbatch_blob_parse", i, [vp, sz, vp]),
+    ("huff_wbatch_verify", i, [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp]),
+    ("huff_diag_wbatch_verify_launches", C.c_uint64, []),
 ]
+
+
+class WBatchBlobView(C.Structure):
+    """huff_wbatch_blob_view (include/huffgpu_wide.h): the header's numbers of a
+    wide batch container and the byte offsets of its sections"""
+    _fields_ = [("width", C.c_uint32), ("nstreams", C.c_uint32), ("has_index", C.c_uint32), ("reserved", C.c_uint32),
+                ("tree_nbits", C.c_uint64), ("comp_bytes", C.c_uint64), ("nsub", C.c_uint64),
+                ("tree_off", C.c_uint64), ("bits_off", C.c_uint64), ("counts_off", C.c_uint64),
+                ("sub_off", C.c_uint64), ("comp_off", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
 
 _lib = None
 
@@ -307,6 +325,11 @@ def wbatch_range_build_launches() -> dict:
     L = load()
     return {L.huff_diag_wbatch_range_build_name(k).decode(): L.huff_diag_wbatch_range_build_launches(k)
             for k in range(L.huff_diag_wbatch_range_builds())}
+
+
+def wbatch_verify_launches() -> int:
+    """launches of k_wbatch_verify so far, process-wide (huff_diag_wbatch_verify_launches): one build, one counter"""
+    return int(load().huff_diag_wbatch_verify_launches())
 
 
 def last_error() -> str:

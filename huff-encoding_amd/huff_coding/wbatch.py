@@ -42,6 +42,19 @@ launches, huff_wbatch_count and huff_wbatch_index, codes of 33-56 bits included:
     counts, status = wbatch_count(ctx, tree, comp, comp_offsets, bits, status_in, seg)
     wbatch_index(ctx, tree, comp, comp_offsets, bits, seg, offsets, index_offsets, status, sub)
 
+A whole batch as ONE container ("HWB1", include/huffgpu_wide.h
+huff_wbatch_to_bytes / huff_wbatch_blob_parse): the tree once, every stream's
+bits and bytes, and (index=True) the letter counts and the restart index. On
+the way back the counts and the index are PROVED against the streams by one
+letter-free launch (huff_wbatch_verify: every 64-letter block must run from its
+entry exactly to the next), so nothing is recounted; a container without index
+takes the from_streams route:
+
+    blob = c.to_bytes(ctx)                                  # bytes; index=False: bits and bytes alone
+    c2 = WideBatchCompressed.from_bytes(ctx, blob)          # c2.status is the proof's verdict per stream
+    status = wbatch_verify(ctx, tree, comp, comp_off, bits, sub, idx_off, offsets, status_in)
+    _lib.wbatch_verify_launches()                           # launches of the proof so far
+
 A stream that cannot be coded gets a status (E_EMPTY_COMP for no letters,
 E_MISSING_LETTER with missing[s] = the index of the first letter without a
 code, E_INVALID_ARG for 2^32 bits or more) and owns no bytes; a stream that
@@ -301,7 +314,46 @@ def wbatch_index(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Te
                                     _p(_never_null(sub)), sub.numel()))
 
 
+def wbatch_verify(ctx, tree: WideTree, comp: torch.Tensor, comp_offsets: torch.Tensor, bits: torch.Tensor,
+                  sub: torch.Tensor, index_offsets: torch.Tensor, offsets: torch.Tensor,
+                  status_in: torch.Tensor) -> torch.Tensor:
+    """huff_wbatch_verify: the per-stream verdict [S] (int32) on letter counts
+    (offsets, their scan) and a restart index (sub, index_offsets) that came
+    from elsewhere: 0 where every 64-letter block runs from its entry exactly
+    to the next, which holds if and only if wbatch_count and wbatch_index would
+    have given these counts and entries; E_CORRUPT otherwise; status_in[s]
+    where that is not 0. One launch, no letter is read or written. The sizes
+    of comp and sub are passed on: a stream whose ranges leave them is
+    E_CORRUPT, nothing outside them is read."""
+    ns = status_in.numel()
+    _dev(comp, torch.uint8)
+    _dev(comp_offsets, torch.int64, (ns + 1,))
+    _dev(bits, torch.int64, (ns,))
+    _dev(sub, torch.int32)
+    _dev(index_offsets, torch.int64, (ns + 1,))
+    _dev(offsets, torch.int64, (ns + 1,))
+    _dev(status_in, torch.int32, (ns,))
+    status = torch.zeros(ns, dtype=torch.int32, device=status_in.device)
+    _check(load().huff_wbatch_verify(ctx.h, tree.h, _p(_never_null(comp)), comp.numel(), _p(comp_offsets), _p(bits),
+                                     _p(_never_null(sub)), sub.numel(), _p(index_offsets), _p(offsets), _p(status_in),
+                                     ns, _p(status)))
+    return status
+
+
+def wbatch_blob_parse(blob) -> dict:
+    """huff_wbatch_blob_parse of a bytes-like container: the header's numbers
+    (width, nstreams, has_index, tree_nbits, comp_bytes, nsub) and the byte
+    offsets of its sections (tree_off, bits_off, counts_off, sub_off,
+    comp_off). Host only; raises HuffError (E_FROM_BYTES) with a text that
+    names what is wrong."""
+    buf = np.frombuffer(blob, np.uint8)
+    view = _lib.WBatchBlobView()
+    _check(load().huff_wbatch_blob_parse(buf.ctypes.data if buf.size else None, buf.size, C.byref(view)))
+    return view.as_dict()
+
+
 _TORCH_OF_WIDTH = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64, 16: torch.uint8}
+_NP_OF_WIDTH = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64, 16: U128}
 
 
 @dataclass
@@ -402,6 +454,76 @@ class WideBatchCompressed:
                 continue
             out.append(WideCompressData.new(comp[lo:hi], int((8 - int(bits[s]) % 8) % 8), self.tree))
         return out
+
+    def to_bytes(self, ctx, index: bool = True) -> bytes:
+        """The whole batch as one "HWB1" container (huff_wbatch_to_bytes;
+        include/huffgpu_wide.h has the format): the tree once, bits and bytes
+        of every stream and, with index, the letter counts and the restart
+        index. A stream whose status is not 0 is stored as a stream of
+        nothing, and from_bytes returns it with status 0 and no letters."""
+        ns = self.status.numel()
+        L = load()
+        size = C.c_size_t()
+        args = (ctx.h, self.tree.h, _p(_never_null(self.comp)), _p(self.comp_offsets), _p(self.bits), _p(self.status),
+                _p(self.offsets), _p(_never_null(self.sub)), _p(self.index_offsets), ns, 1 if index else 0)
+        _check(L.huff_wbatch_to_bytes(*args, None, 0, C.byref(size)))
+        out = np.empty(size.value, np.uint8)
+        _check(L.huff_wbatch_to_bytes(*args, out.ctypes.data, out.size, C.byref(size)))
+        return out.tobytes()
+
+    @staticmethod
+    def from_bytes(ctx, blob, letters_dtype: torch.dtype = None, verify: bool = True) -> "WideBatchCompressed":
+        """The batch of a container that to_bytes wrote, here or in another
+        process. huff_wbatch_blob_parse (shape and size of untrusted bytes;
+        HuffError E_FROM_BYTES names what is wrong), the tree from its stored
+        bits (letters of 1, 2, 4 and 8 bytes as unsigned integers, 16 as
+        wide.U128), one upload per section, and the three offset arrays as the
+        scans of ceil(bits / 8), counts and ceil(counts / 64).
+
+        With the index the counts and entries are proved against the streams
+        by one launch of wbatch_verify, and the result's status is the proof's:
+        E_CORRUPT for a stream whose numbers, entries or bytes do not agree,
+        its neighbours intact. Without the index the route is from_streams,
+        unchanged (wbatch_count + wbatch_index).
+
+        verify=False takes the arrays as they are, every status 0. That is
+        safe: huff_wbatch_decode and huff_wbatch_decode_ranges check every
+        block they touch against its entries and read and write nothing
+        outside a stream's own ranges, so a bad stream still ends as E_CORRUPT
+        when it is decoded. What is lost is only the early verdict per stream
+        (and decompress_batch sizes its output by the stored counts)."""
+        v = wbatch_blob_parse(blob)
+        buf = np.frombuffer(blob, np.uint8)
+        width, ns = v["width"], v["nstreams"]
+        if letters_dtype is None:
+            letters_dtype = _TORCH_OF_WIDTH[width]
+        elif torch.empty(0, dtype=letters_dtype).element_size() not in (1, width):
+            raise TypeError(f"{letters_dtype} does not hold letters of {width} bytes")
+        h = C.c_void_p()
+        _check(load().huff_wtree_try_from_bin(width, buf[v["tree_off"]:].ctypes.data, v["tree_nbits"], C.byref(h)))
+        tree = WideTree(h, LetterType(_NP_OF_WIDTH[width]))
+        dev = torch.device("cuda")
+
+        def upload(np_dtype, count, off):
+            # the sections start on 8-byte boundaries of the blob; a copy gives numpy an aligned, writable array
+            a = np.frombuffer(blob, np.uint8, count * np.dtype(np_dtype).itemsize, off).copy().view(np_dtype)
+            return torch.from_numpy(a).to(dev)
+
+        bits = upload(np.int64, ns, v["bits_off"])  # < 2^32 each
+        comp = upload(np.uint8, v["comp_bytes"], v["comp_off"])
+        comp_offsets = _scan((bits + 7) // 8)
+        if not v["has_index"]:
+            return WideBatchCompressed.from_streams(ctx, tree, comp, comp_offsets, bits=bits, letters_dtype=letters_dtype)
+        counts = upload(np.int64, ns, v["counts_off"])  # ceil(counts / 64) add up to nsub: far below 2^63
+        sub = upload(np.int32, v["nsub"], v["sub_off"])
+        offsets = _scan(counts)
+        index_offsets = _scan((counts + (IDX - 1)) // IDX)
+        status = torch.zeros(ns, dtype=torch.int32, device=dev)
+        if verify:
+            status = wbatch_verify(ctx, tree, comp, comp_offsets, bits, sub, index_offsets, offsets, status)
+        missing = torch.full((ns,), -1, dtype=torch.int64, device=dev)
+        return WideBatchCompressed(comp, comp_offsets, bits, sub, index_offsets, status, missing, offsets, tree, width,
+                                   letters_dtype)
 
 
 def compress_batch(ctx, letters: torch.Tensor, offsets: torch.Tensor, tree: WideTree) -> WideBatchCompressed:

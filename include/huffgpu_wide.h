@@ -522,7 +522,149 @@ int huff_wbatch_index(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp,
                       const uint64_t* d_index_offsets, uint32_t* d_status, uint32_t nstreams, uint32_t* d_sub,
                       size_t sub_cap);
 
+/* A whole wide batch as ONE container, and the proof of its letter counts and
+ * restart index on the way back ("A wide batch as one container";
+ * csrc/host/wbatch_blob.hpp, csrc/device/wbatch_verify.hip). The tree is stored
+ * once, not per stream. Little-endian; every section starts on an 8-byte
+ * boundary counted from the blob's first byte, with zero fill between sections:
+ *
+ *   "HWB1"  u32 width (1,2,4,8,16)  u32 nstreams  u32 flags (bit 0: counts and index present; other bits 0)
+ *   u64 tree_nbits  u64 comp_bytes  u64 nsub (0 without index)  u64 reserved = 0
+ *   tree bits      ceil(tree_nbits / 8) bytes: huff_wtree_as_bin, MSB first, zero tail
+ *   u64 bits[nstreams]
+ *   u64 counts[nstreams]     only with flag bit 0
+ *   u32 sub[nsub]            only with flag bit 0: the streams' entries one after another
+ *   comp           comp_bytes bytes: the streams, tight, stream s = ceil(bits[s] / 8) bytes
+ *
+ * d_comp_offsets, d_offsets and d_index_offsets are not stored: they are the
+ * exclusive scans of ceil(bits / 8), counts and ceil(counts / 64). A stream
+ * whose status is not HUFF_OK (no letters, a missing letter, 2^32 bits) is
+ * stored as a stream of 0 bits, 0 letters and no entries, the entries that
+ * huff_wbatch_bits reserved for it dropped, and comes back with status 0 and no
+ * letters, as a stream of no bytes does from huff_wbatch_count.
+ *
+ *  huff_wbatch_blob_size: host only. The bytes of the container of nstreams
+ *                      streams of comp_bytes bytes in all with nsub entries in
+ *                      all under t. HUFF_E_INVALID_ARG for a null pointer, nsub
+ *                      != 0 without with_index, or a size past size_t.
+ *  huff_wbatch_to_bytes: the batch that huff_wbatch_bits / _pack (or _count /
+ *                      _index) left in the device arrays, into the host buffer
+ *                      out. *out_len is always the container's size; out NULL
+ *                      with cap 0 asks for it alone; a short cap gives
+ *                      HUFF_E_BUFFER_TOO_SMALL with nothing written. with_index
+ *                      0: bits and bytes alone (d_offsets, d_sub and
+ *                      d_index_offsets are not read and may be NULL). When no
+ *                      stream is dropped, sub and comp go from device memory
+ *                      straight to their places in out, in one copy each.
+ *                      HUFF_E_INVALID_ARG before any payload is copied: a null
+ *                      pointer (with_index set: d_sub, d_offsets and
+ *                      d_index_offsets too), or a HUFF_OK stream whose layout
+ *                      is not the tight one (2^32 bits or more, bytes other
+ *                      than ceil(bits / 8), entries other than ceil(n_s / 64)).
+ *                      HUFF_E_CODE_TOO_LONG as for the other huff_wbatch_*
+ *                      calls.
+ *  huff_wbatch_blob_parse: host only, no context. Takes untrusted bytes and
+ *                      checks shape and size alone; the view holds the header's
+ *                      numbers and the byte offsets within the blob of the five
+ *                      sections (counts_off and sub_off mean nothing without
+ *                      the index). The tree is then huff_wtree_try_from_bin(
+ *                      width, blob + tree_off, tree_nbits, ...). Every failure
+ *                      is HUFF_E_FROM_BYTES with a text that names it: a short
+ *                      blob; another magic (HFW1 and HFX1, the index sidecars
+ *                      of single streams, are refused by name); a width not
+ *                      among the five; unknown flag bits, a non-zero reserved
+ *                      word or non-zero fill bytes; nsub != 0 without the flag;
+ *                      any bits[s] >= 2^32; sum ceil(bits / 8) != comp_bytes;
+ *                      with the flag, sum ceil(counts / 64) != nsub; trailing
+ *                      bytes. No arithmetic on a number read from the blob can
+ *                      wrap. What is wrong about one stream alone (counts[s] >
+ *                      bits[s], a bad entry, a flipped payload bit) is not the
+ *                      parser's business: it becomes that stream's status in
+ *                      huff_wbatch_verify, and its neighbours stay intact.
+ *  huff_wbatch_verify: the proof, in one launch, synchronous on the context's
+ *                      stream; device pointers, the batch described as for
+ *                      huff_wbatch_decode, comp_bytes and sub_entries the sizes
+ *                      of d_comp and d_sub. d_status[s], the first that applies:
+ *                       d_status_in[s]   if that is not HUFF_OK; nothing of the
+ *                                        stream is read.
+ *                       HUFF_E_CORRUPT   the stream's byte range leaves
+ *                                        comp_bytes or its entry range leaves
+ *                                        sub_entries.
+ *                       HUFF_E_CORRUPT   the stream's own numbers disagree, as
+ *                                        for huff_wbatch_decode (d_bits[s] >=
+ *                                        2^32, bytes other than ceil(bits / 8),
+ *                                        n_s > bits, entries other than
+ *                                        ceil(n_s / 64)).
+ *                       HUFF_E_CORRUPT   n_s == 0 with bits > 0. Here the proof
+ *                                        is STRICTER than huff_wbatch_decode,
+ *                                        which passes such a stream and writes
+ *                                        nothing: a proof must show that n_s IS
+ *                                        the stream's count.
+ *                       HUFF_OK          0 bits and 0 letters.
+ *                       HUFF_E_CORRUPT   a block j whose entry 0 is not 0, whose
+ *                                        entries are out of order or past
+ *                                        d_bits[s], or from whose entry the
+ *                                        min(64, n_s - 64 j) codes do not end
+ *                                        exactly at entry j + 1 (the last
+ *                                        block: at d_bits[s]); a window without
+ *                                        a code or a code crossing the block's
+ *                                        end is that.
+ *                       HUFF_OK          otherwise.
+ *                      By induction from entry 0 = 0 the last rule holds IF AND
+ *                      ONLY IF huff_wbatch_count answers HUFF_OK with this count
+ *                      for the stream and huff_wbatch_index writes exactly these
+ *                      entries: the serial walk from bit 0 passes every entry
+ *                      after 64 codes each and ends at d_bits[s] after n_s. A
+ *                      batch that passes is the batch count + index would have
+ *                      built. Before any device work: HUFF_E_INVALID_ARG for a
+ *                      null pointer, HUFF_E_CODE_TOO_LONG for a tree with a
+ *                      code longer than 56 bits; nstreams == 0: HUFF_OK, no
+ *                      launch. Whatever the arrays hold, a stream reads only
+ *                      its own bytes (zero past them), its own entries and the
+ *                      tree's tables, and writes d_status[s] only.
+ *
+ * Nothing is guessed and nothing is iterated: a wave takes a stream, a lane a
+ * 64-letter block, each code is looked up once; only code lengths are read (the
+ * primary table staged once per persistent workgroup of 16 waves), no leaf
+ * letter is read and no output is written, so one kernel serves every letter
+ * width. The proof does the decode's reads without the leaf reads and the
+ * stores.
+ * Cost, measured on an MI355X on huff_wbatch_decode's batches above
+ * (tools/wbatchcontainerbench.py, DESIGN.md §9, "A wide batch as one
+ * container"; kernel times, medians of 10, one process, the calls alternating,
+ * beside huff_wbatch_decode and huff_wbatch_count + _index of the same batch;
+ * 2- / 4-byte letters, Zipf then uniform): the proof takes 0.44 / 0.44 and
+ * 3.09 / 5.17 ms, 0.76 / 0.58 and 1.04 / 0.76 of one huff_wbatch_decode, where
+ * count + index take 1.26 / 1.26 and 0.81 / 239 ms. ON THE 2-BYTE UNIFORM BATCH
+ * THE PROOF IS 4 % SLOWER THAN THE DECODE (3.09 against 2.97 ms, whose runs
+ * spread 2.94-3.00 ms): every code there is 16 bits and costs a dependent read
+ * of the secondaries in L2 in either kernel, and count + index is the cheaper
+ * route to the same arrays. On the 2^20-letter batch the proof replaces 239 ms
+ * by 5.2 ms. Wall times of to_bytes / from_bytes in Python (host copies of
+ * 70-215 MB around those kernels): 25-84 / 11-35 ms on the first three batches,
+ * 679 / 670 ms on the 2^20-letter batch, where serialising the tree and
+ * building the new tree's decode tables on the host dominate. */
+typedef struct huff_wbatch_blob_view {
+    uint32_t width, nstreams, has_index, reserved;
+    uint64_t tree_nbits, comp_bytes, nsub;
+    uint64_t tree_off, bits_off, counts_off, sub_off, comp_off;
+} huff_wbatch_blob_view;
+int huff_wbatch_blob_size(const huff_wtree* t, uint32_t nstreams, size_t comp_bytes, size_t nsub, int with_index,
+                          size_t* size);
+int huff_wbatch_to_bytes(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, const uint64_t* d_comp_offsets,
+                         const uint64_t* d_bits, const uint32_t* d_status, const uint64_t* d_offsets,
+                         const uint32_t* d_sub, const uint64_t* d_index_offsets, uint32_t nstreams, int with_index,
+                         uint8_t* out, size_t cap, size_t* out_len);
+int huff_wbatch_blob_parse(const uint8_t* blob, size_t len, huff_wbatch_blob_view* view);
+int huff_wbatch_verify(huff_ctx* ctx, const huff_wtree* t, const uint8_t* d_comp, size_t comp_bytes,
+                       const uint64_t* d_comp_offsets, const uint64_t* d_bits, const uint32_t* d_sub, size_t sub_entries,
+                       const uint64_t* d_index_offsets, const uint64_t* d_offsets, const uint32_t* d_status_in,
+                       uint32_t nstreams, uint32_t* d_status);
+
 /* ---------------- diagnostics (not reference functions) ------------------ */
+/* huff_wbatch_verify has one build for all letter widths and no table of its
+ * own: one process-wide count of its launches. */
+uint64_t huff_diag_wbatch_verify_launches(void);
 /* huff_wbatch_* take their kernels from tables of their own: 20 k_wbatch_bits
  * rows (letter width x u64 or u32 table values x table in LDS or read in
  * place), 30 k_wbatch_pack rows (the same with the three entry formats: codes
