@@ -4,7 +4,8 @@
 // (letter << 8 | len) in LDS built from the stream's d_codes row, the list of
 // the letters whose codes are longer than the table's index, and the readers of
 // a stream's compressed bytes as big-endian words, from global memory or from a
-// staged copy in LDS.
+// staged copy in LDS. The readers and batch_window also serve the wide batch
+// kernels (wbatch_walk.hpp).
 #pragma once
 
 #include "kernels.hpp"
@@ -104,6 +105,14 @@ __device__ __forceinline__ void batch_build_lut(const uint64_t* __restrict__ cod
         for (uint32_t i = t; i < sp; i += TH) lut[first + i] = static_cast<uint16_t>((l << 8) | ll);
     }
     __syncthreads();
+}
+
+// 64 bits of the stream from bit pos, left-aligned
+template <class Src>
+__device__ __forceinline__ uint64_t batch_window(const Src& src, uint32_t pos) {
+    const uint32_t wi = pos >> 5, sh = pos & 31;
+    const uint64_t hi = (static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1);
+    return sh ? (hi << sh) | (src.word(wi + 2) >> (32 - sh)) : hi;
 }
 
 // the code at bit `pos` among the long codes, searched left-aligned: its

@@ -53,7 +53,7 @@ namespace {
 
 constexpr uint32_t kThreads = kWBatchWaves * 64;
 constexpr size_t kLetterLdsMax = 32 * 1024;  // stage the decoder's leaf letters in LDS up to this (as wide.hip)
-static_assert(kWBatchBlock == kWideRun && kWBatchBlock == kIdx, "one restart entry per 64 letters, as every index here");
+static_assert(kWBatchBlock == kWideRun, "one restart entry per 64 letters, as the single-stream wide path");
 
 // the lane's letters of a tile (p: the stream's first letter; aligned to the
 // letter only). A full lane loads its bytes whole, the tail letter by letter.
@@ -374,10 +374,10 @@ hipError_t launch_wbatch_pack(const WBatchEncArgs& a, hipStream_t s) {
 
 hipError_t launch_wbatch_decode(const WBatchDecArgs& a, hipStream_t s) {
     if (a.nstreams == 0) return hipSuccess;
-    if (a.lut_bits == 0 || a.lut_bits > kLutMaxBits || a.nleaves == 0 || !a.sub) return hipErrorInvalidValue;
+    if (!wbatch_table_ok(a.lut, a.lut_bits) || a.nleaves == 0 || !a.sub) return hipErrorInvalidValue;
     const uint32_t wi = width_index(a.width);
     if (a.width != (1u << wi)) return hipErrorInvalidValue;
-    const size_t prim = ((size_t(4) << a.lut_bits) + 15) & ~size_t(15);
+    const size_t prim = wbatch_prim_lds(a.lut_bits);
     const size_t lw = (static_cast<size_t>(a.nleaves) * a.width + 15) / 16 * 16;
     const bool llds = lw <= kLetterLdsMax;
     if (wi == 0 && !llds) return hipErrorInvalidValue;  // no such build: more byte leaves than byte values

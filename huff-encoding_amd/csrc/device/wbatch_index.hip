@@ -43,8 +43,8 @@
 // (BatchSrc / BatchSrcLds give zero past them), its own segment entries (inside
 // seg_cap), counts[s], status[s] and its own entries of sub (inside sub_cap).
 #include "../host/wbatch_index_plan.hpp"
-#include "batch_stream.hpp"
 #include "bitreader.hpp"
+#include "wbatch_walk.hpp"
 
 namespace huff::dev {
 
@@ -53,15 +53,6 @@ namespace {
 constexpr uint32_t kThreads = kWBatchIdxLanes;
 constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint64_t kWalkBad = kWBatchWalkBad;
-static_assert(kWBatchBlock == kIdx, "one restart entry per 64 letters, as every index here");
-
-// 64 bits of the stream from bit pos, left-aligned
-template <class Src>
-__device__ __forceinline__ uint64_t window_at(const Src& src, uint32_t pos) {
-    const uint32_t wi = pos >> 5, sh = pos & 31;
-    const uint64_t hi = (static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1);
-    return sh ? (hi << sh) | (src.word(wi + 2) >> (32 - sh)) : hi;
-}
 
 // The codes from bit `pos` up to the first boundary at or past `seg_end`
 // (<= end_all); at(p, i) sees the i-th of them at bit p. Returns that boundary
@@ -85,7 +76,7 @@ __device__ __forceinline__ uint64_t seg_walk(const Src& src, uint32_t pos, uint3
         }
         uint32_t e = prim[buf >> (64 - K)];
         if ((e & kLutPtr) || ((e >> 24) & 0x7Fu) > nb) {
-            const uint64_t win = window_at(src, pos);
+            const uint64_t win = batch_window(src, pos);
             e = prim[win >> (64 - K)];
             for (uint32_t d = K; (e & kLutPtr) && d <= 56; d += 8)
                 e = glob[(e & ~kLutPtr) + static_cast<uint32_t>((win >> (56 - d)) & 0xFFu)];
@@ -109,12 +100,6 @@ __device__ __forceinline__ uint64_t seg_walk(const Src& src, uint32_t pos, uint3
     return pos;
 }
 
-// the primary table into LDS, once per workgroup
-__device__ __forceinline__ void stage_prim(uint32_t* __restrict__ plut, const uint32_t* __restrict__ lut, uint32_t K) {
-    for (uint32_t i = threadIdx.x; i < (1u << K); i += kThreads) plut[i] = lut[i];
-    __syncthreads();
-}
-
 // the round's bytes into LDS
 __device__ __forceinline__ BatchSrcLds stage_round(uint8_t* __restrict__ cst, const BatchSrc& src, uint32_t r0) {
     const WBatchStage st = wbatch_round_stage(src.nbytes, r0);
@@ -130,7 +115,8 @@ __global__ __launch_bounds__(kThreads) void k_wbatch_count(WBatchCountArgs a) {
     __shared__ uint64_t ex[kThreads];
     __shared__ uint32_t wsum[kWaves];
     const uint32_t t = threadIdx.x, lane = t & 63, K = a.lut_bits;
-    stage_prim(plut, a.lut, K);
+    wbatch_stage_prim<kThreads>(plut, a.lut, K);
+    __syncthreads();
     auto none = [](uint32_t, uint32_t) {};
     for (uint64_t s = blockIdx.x; s < a.nstreams; s += gridDim.x) {
         // every early exit below is workgroup-uniform: it depends on the stream's numbers alone
@@ -215,7 +201,8 @@ __global__ __launch_bounds__(kThreads) void k_wbatch_index(WBatchIndexArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t plut[];  // 1 << lut_bits primary entries
     __shared__ __attribute__((aligned(16))) uint8_t cst[kWBatchStageBytes];
     const uint32_t t = threadIdx.x, K = a.lut_bits;
-    stage_prim(plut, a.lut, K);
+    wbatch_stage_prim<kThreads>(plut, a.lut, K);
+    __syncthreads();
     for (uint64_t s = blockIdx.x; s < a.nstreams; s += gridDim.x) {
         // every early exit below is workgroup-uniform
         if (a.status[s] != kBatchOk) continue;
@@ -254,18 +241,15 @@ __global__ __launch_bounds__(kThreads) void k_wbatch_index(WBatchIndexArgs a) {
     }
 }
 
-// the workgroup's LDS: the primary table (dynamic) beside the static stage and exits
-size_t lds_bytes(uint32_t lut_bits) { return ((size_t(4) << lut_bits) + 15) & ~size_t(15); }
+// the workgroup's LDS beside the primary table (dynamic): the static stage and exits
 constexpr size_t kStaticLds = kWBatchStageBytes + kThreads * 8 + 64;
-
-bool table_ok(uint32_t lut_bits, const uint32_t* lut) { return lut && lut_bits != 0 && lut_bits <= kLutMaxBits; }
 
 }  // namespace
 
 hipError_t launch_wbatch_count(const WBatchCountArgs& a, hipStream_t s) {
     if (a.nstreams == 0) return hipSuccess;
-    if (!table_ok(a.lut_bits, a.lut)) return hipErrorInvalidValue;
-    const size_t lds = lds_bytes(a.lut_bits);
+    if (!wbatch_table_ok(a.lut, a.lut_bits)) return hipErrorInvalidValue;
+    const size_t lds = wbatch_prim_lds(a.lut_bits);
     launch_k(k_wbatch_count, dim3(wbatch_index_grid(a.nstreams, a.cu_count, lds + kStaticLds)), dim3(kThreads),
              static_cast<uint32_t>(lds), s, a);
     return hipGetLastError();
@@ -273,8 +257,8 @@ hipError_t launch_wbatch_count(const WBatchCountArgs& a, hipStream_t s) {
 
 hipError_t launch_wbatch_index(const WBatchIndexArgs& a, hipStream_t s) {
     if (a.nstreams == 0) return hipSuccess;
-    if (!table_ok(a.lut_bits, a.lut)) return hipErrorInvalidValue;
-    const size_t lds = lds_bytes(a.lut_bits);
+    if (!wbatch_table_ok(a.lut, a.lut_bits)) return hipErrorInvalidValue;
+    const size_t lds = wbatch_prim_lds(a.lut_bits);
     launch_k(k_wbatch_index, dim3(wbatch_index_grid(a.nstreams, a.cu_count, lds + kStaticLds)), dim3(kThreads),
              static_cast<uint32_t>(lds), s, a);
     return hipGetLastError();

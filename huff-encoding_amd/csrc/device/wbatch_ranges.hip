@@ -128,10 +128,10 @@ uint64_t wbatch_range_build_launches(uint32_t i) {
 
 hipError_t launch_wbatch_decode_ranges(const WBatchRangesArgs& a, hipStream_t s) {
     if (a.nreq == 0) return hipSuccess;
-    if (a.lut_bits == 0 || a.lut_bits > kLutMaxBits || a.nleaves == 0 || !a.sub) return hipErrorInvalidValue;
+    if (!wbatch_table_ok(a.lut, a.lut_bits) || a.nleaves == 0 || !a.sub) return hipErrorInvalidValue;
     const uint32_t wi = a.width == 1 ? 0u : a.width == 2 ? 1u : a.width == 4 ? 2u : a.width == 8 ? 3u : 4u;
     if (a.width != (1u << wi)) return hipErrorInvalidValue;
-    const size_t prim = ((size_t(4) << a.lut_bits) + 15) & ~size_t(15);
+    const size_t prim = wbatch_prim_lds(a.lut_bits);
     const size_t lw = (static_cast<size_t>(a.nleaves) * a.width + 15) / 16 * 16;
     const bool llds = lw <= kLetterLdsMax;
     if (wi == 0 && !llds) return hipErrorInvalidValue;  // no such build: more byte leaves than byte values

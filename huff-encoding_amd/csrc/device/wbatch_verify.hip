@@ -23,33 +23,25 @@
 // stream's bytes are read through BatchSrc from global memory, as the decode
 // reads them.
 //
-// The walker below is the third copy of the length walk of decode_block
-// (wbatch_walk.hpp) and seg_walk (wbatch_index.hip). Those two are not lifted
-// into one: decode_block gathers letters inside the loop and seg_walk calls back
-// per code, and any shared form would change the code compiled for kernels this
-// file must leave as they are.
+// walk_block below holds the same length walk as decode_block (wbatch_walk.hpp)
+// and seg_walk (wbatch_index.hip); a fix to one is a fix to all three. They
+// share the window read (batch_stream.hpp's batch_window) and the table's
+// launch-side helpers (wbatch_walk.hpp), not the step: one step under the three
+// loops was built and measured 2 to 5 % slower than these copies on an MI355X,
+// twice ("Three walkers"; profiles/wbatch_walker/).
 //
 // What a stream can touch, whatever the arrays hold: its own compressed bytes
 // (BatchSrc gives zero past them), its own entries, the tables, and status[s].
 #include <atomic>
 
-#include "../host/wbatch_plan.hpp"
-#include "batch_stream.hpp"
 #include "bitreader.hpp"
+#include "wbatch_walk.hpp"
 
 namespace huff::dev {
 
 namespace {
 
 constexpr uint32_t kThreads = kWBatchWaves * 64;
-static_assert(kWBatchBlock == kIdx, "one restart entry per 64 letters, as every index here");
-
-// 64 bits of the stream from bit pos, left-aligned
-__device__ __forceinline__ uint64_t window_at(const BatchSrc& src, uint32_t pos) {
-    const uint32_t wi = pos >> 5, sh = pos & 31;
-    const uint64_t hi = (static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1);
-    return sh ? (hi << sh) | (src.word(wi + 2) >> (32 - sh)) : hi;
-}
 
 // cnt codes from bit `start` (start <= end) must end exactly at bit `end`.
 // False: a window without a code, a code crossing `end`, or an end other than
@@ -69,7 +61,7 @@ __device__ __forceinline__ bool walk_block(const BatchSrc& src, const uint32_t* 
         }
         uint32_t e = prim[buf >> (64 - K)];
         if ((e & kLutPtr) || ((e >> 24) & 0x7Fu) > nb) {
-            const uint64_t win = window_at(src, pos);
+            const uint64_t win = batch_window(src, pos);
             e = prim[win >> (64 - K)];
             for (uint32_t d = K; (e & kLutPtr) && d <= 56; d += 8)
                 e = glob[(e & ~kLutPtr) + static_cast<uint32_t>((win >> (56 - d)) & 0xFFu)];
@@ -147,8 +139,8 @@ std::atomic<uint64_t> g_launches{0};
 
 hipError_t launch_wbatch_verify(const WBatchVerifyArgs& a, hipStream_t s) {
     if (a.nstreams == 0) return hipSuccess;
-    if (!a.lut || a.lut_bits == 0 || a.lut_bits > kLutMaxBits) return hipErrorInvalidValue;
-    const size_t lds = ((size_t(4) << a.lut_bits) + 15) & ~size_t(15);
+    if (!wbatch_table_ok(a.lut, a.lut_bits)) return hipErrorInvalidValue;
+    const size_t lds = wbatch_prim_lds(a.lut_bits);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     launch_k(k_wbatch_verify, dim3(persistent_grid(a.nstreams, a.cu_count, lds)), dim3(kThreads),
              static_cast<uint32_t>(lds), s, a);

@@ -3,7 +3,12 @@
 // k_wbatch_decode_ranges (wbatch_ranges.hip): from the block's restart entry
 // through WideDecTables::lut (primary table at `prim`, 8-bit secondaries in
 // global memory) to exactly the next entry. The stream's bytes are read
-// through BatchSrc, 32-bit positions, zero past the end.
+// through BatchSrc, 32-bit positions, zero past the end. Also what all five
+// wide batch kernels (these two, k_wbatch_count and k_wbatch_index in
+// wbatch_index.hip, k_wbatch_verify in wbatch_verify.hip) share about the
+// primary table. The walk itself exists three times, here, as seg_walk and as
+// walk_block, and a change to one belongs in all three ("Three
+// walkers": one shared step measured slower).
 #pragma once
 
 #include "../host/wbatch_plan.hpp"
@@ -13,11 +18,21 @@
 
 namespace huff::dev {
 
-// 64 bits of the stream from bit pos, left-aligned
-__device__ __forceinline__ uint64_t src_window(const BatchSrc& src, uint32_t pos) {
-    const uint32_t wi = pos >> 5, sh = pos & 31;
-    const uint64_t hi = (static_cast<uint64_t>(src.word(wi)) << 32) | src.word(wi + 1);
-    return sh ? (hi << sh) | (src.word(wi + 2) >> (32 - sh)) : hi;
+static_assert(kWBatchBlock == kIdx, "one restart entry per 64 letters, as every index here");
+
+// The primary table of WideDecTables::lut, which all five kernels of a wide
+// batch stage in LDS once per workgroup: its size there (1 << lut_bits entries,
+// to a whole 16 bytes), what a launch refuses before it sizes anything by
+// lut_bits, and the copy by a workgroup of TH lanes (the caller's barrier
+// completes it; count and index use it, the other three keep the loop written
+// out, which is what leaves their compiled code as it was).
+inline size_t wbatch_prim_lds(uint32_t lut_bits) { return ((size_t(4) << lut_bits) + 15) & ~size_t(15); }
+inline bool wbatch_table_ok(const uint32_t* lut, uint32_t lut_bits) {
+    return lut && lut_bits != 0 && lut_bits <= kLutMaxBits;
+}
+template <uint32_t TH>
+__device__ __forceinline__ void wbatch_stage_prim(uint32_t* plut, const uint32_t* lut, uint32_t K) {
+    for (uint32_t i = threadIdx.x; i < (1u << K); i += TH) plut[i] = lut[i];
 }
 
 // cnt codes from bit `start`, which must end exactly at bit `end` (start <=
@@ -51,7 +66,7 @@ __device__ __forceinline__ bool decode_block(const BatchSrc& src, const uint32_t
                 }
                 uint32_t e = prim[buf >> (64 - K)];
                 if ((e & kLutPtr) || ((e >> 24) & 0x7Fu) > nb) {
-                    const uint64_t win = src_window(src, pos);
+                    const uint64_t win = batch_window(src, pos);
                     e = prim[win >> (64 - K)];
                     for (uint32_t d = K; (e & kLutPtr) && d <= 56; d += 8)
                         e = glob[(e & ~kLutPtr) + static_cast<uint32_t>((win >> (56 - d)) & 0xFFu)];
