@@ -48,16 +48,29 @@ class Packed:
         lengths = LENGTHS + [300] + [int(x) for x in rng.integers(1, 10_000, 3)]
         idx = _stream_idx(case, rng, len(lengths), lengths=lengths)
         idx[S_MISSING][137] = case.coded  # the letter without a code
-        self.b = b = Batch(torch, case, idx)
-        self.p = _pack(torch, ctx, b)
-        self.W = width
-        self.n = [len(x) for x in idx]
-        self.rows = np.frombuffer(b.letters_np.tobytes(), np.uint8).reshape(-1, width)  # a row per letter
-        self.status = self.p["status"].cpu().numpy()
+        b = Batch(torch, case, idx)
+        self._adopt(b, _pack(torch, ctx, b))
         want = [E_EMPTY if n == 0 else OK for n in self.n]
         want[S_MISSING] = E_MISSING
         assert list(self.status) == want
-        self.build = case.builds()[2].replace("k_wbatch_decode<", "k_wbatch_decode_ranges<")
+
+    def _adopt(self, b, p):
+        self.case, self.b, self.p, self.W = b.case, b, p, b.case.width
+        self.n = [len(x) for x in b.idx]
+        self.rows = np.frombuffer(b.letters_np.tobytes(), np.uint8).reshape(-1, self.W)  # a row per letter
+        self.status = p["status"].cpu().numpy()
+        self.build = b.case.builds()[2].replace("k_wbatch_decode<", "k_wbatch_decode_ranges<")
+
+    @classmethod
+    def of(cls, b, p, rows=None):
+        """a Batch and its _pack result that another file made, as _run, _check and _truth take them.
+        rows (default: the batch's letters, a row each): what letters() answers with"""
+        pk = cls.__new__(cls)
+        pk._adopt(b, p)
+        if rows is not None:
+            assert rows.shape == pk.rows.shape and rows.dtype == pk.rows.dtype
+            pk.rows = rows
+        return pk
 
     def letters(self, s, f, m):
         lo = int(self.b.offs_np[s])
